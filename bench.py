@@ -12,9 +12,13 @@ predicted frames depend on the actions -- synthetic.synth_state_dict; fp32 stora
          losses, backward, (N>1: RCCL gradient all-reduce), fused Adam, loss readback.  `value` = frames/s.
   cem:   configs[2] -- 1000 candidates per GPU x horizon 15 (14 model steps) through the frozen model;
          one "iteration" = generate_model_rollouts (N>1: candidates sharded, one all-gather of the costs).
-After the timed regions rank 0 (N = 1) runs the CPU oracle on a bounded sample of the same workloads: that is the
-`cpu_baseline`, and the same numbers are asserted against the GPU's (train losses of one step at the full batch,
+A plain run measures the headline alone: it sets up the train workload, warms it up, times --steps steps and prints the
+line (`value` = train frames/s, `ms_per_step`).  `--full` adds everything else the benchmark measures and checks: the cem
+workloads (and the planner's get_action), the side configurations, the exact-fp32 runs, both gradient-exchange modes
+(N > 1) and, after the timed regions on rank 0 (N = 1), the CPU oracle on a bounded sample of the same workloads: that
+is the `cpu_baseline`, and the same numbers are asserted against the GPU's (train losses of one step at the full batch,
 sum_cost of 64 of the 1000 candidates) -- the benchmark refuses to print a line for a path that has drifted.
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (write_outputs).
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -78,6 +82,47 @@ F32_MFMA_PEAK_TFLOPS = 157.3
 TRAIN_FWD_GFLOP_PER_SAMPLE_STEP = 36.26   # SURVEY.md 8d, hook-counted on the reference (g512/z64, 64x64, RA flags)
 CEM_FWD_GFLOP_PER_CAND_STEP = 24.46
 CEM_CHECK_TOP, CEM_CHECK_OTHERS = 32, 32  # the oracle re-rolls the GPU's own top 32 candidates and 32 random others
+DUMP_SAMPLE = 1 << 17  # --dump-outputs: elements kept of one state tensor (a fixed, seeded sample of a larger one)
+DUMP_LIMIT = 64 << 20  # --dump-outputs: bytes in all
+
+
+def state_sample(model):
+    """The model's floating-point state (weights, BatchNorm statistics) as float32 arrays: a tensor of up to DUMP_SAMPLE
+    elements whole, a larger one at DUMP_SAMPLE flat positions drawn from a generator seeded by its name (the same
+    positions in every run and every build)."""
+    import zlib
+    out = {}
+    for name, t in model.state_dict().items():
+        if not t.is_floating_point():
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        out[name] = flat.float().cpu().numpy()
+    return out
+
+
+def write_outputs(path, train, cem, cem_ra):
+    """--dump-outputs: what the timed paths computed in their last step, one DIR/<name>.npy per array.  train: the loss
+    terms `_train_step` returned (float64) and the model's state after that step's optimiser update (float32,
+    state_sample); cem / cem_ra: every candidate's sum_cost of the last timed rollout (float64)."""
+    arrays = {}
+    if train is not None:
+        for k, v in sorted(train["outputs"]["losses"].items()):
+            arrays[f"train.loss.{k}"] = np.array([v], np.float64)
+        for k, v in train["outputs"]["state"].items():
+            arrays[f"train.state.{k}"] = v
+    for tag, c in (("cem", cem), ("cem_ra", cem_ra)):
+        if c is not None:
+            arrays[f"{tag}.sum_cost"] = np.asarray(c["outputs"]["sum_cost"], np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT}"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    log(f"wrote {len(arrays)} arrays ({total / 2**20:.1f} MiB) to {path}")
 
 
 
@@ -128,8 +173,12 @@ def namespace(dev, **kw):
     return argparse.Namespace(**d)
 
 
+def rank_of_env():
+    return int(os.environ.get("RANK", 0))
+
+
 def log(msg):
-    if int(os.environ.get("RANK", 0)) == 0:
+    if rank_of_env() == 0:
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
@@ -298,13 +347,15 @@ def build_train(args, dev):
     return cf, tr
 
 
-def bench_train(args, dev, rank, world, distributed, exact_of=None):
+def bench_train(args, dev, rank, world, distributed, exact_of=None, dump=False):
     """`exact_of`: the result of the split-precision run whose first step (same weights, data, noise) this run repeats
-    with every conv on the exact-fp32 MFMA kernels (ops.SPLIT_GEMM off): a shorter timed region, no CPU check."""
+    with every conv on the exact-fp32 MFMA kernels (ops.SPLIT_GEMM off): a shorter timed region, no CPU check.
+    `dump`: keep what the last timed step computed (`outputs`: its losses and the model's state after it)."""
     cf, tr = build_train(args, dev)
     B, T = cf.batch_size, cf.n_past + cf.n_future
     side_cfg = args.h48 or args.cfg5 or args.group_norm or getattr(args, "deployed", False) or getattr(args, "sched", None)
-    want_check = rank == 0 and world == 1 and not args.no_cpu_baseline and not side_cfg and exact_of is None
+    want_check = (rank == 0 and world == 1 and getattr(args, "full", False) and not args.no_cpu_baseline and not side_cfg
+                  and exact_of is None)
     # scheduled sampling with the coin forced (trainer.py:132-147,354): frame i of the window is ground truth or the model's
     # own prediction of it; "all": every frame after the first is fed back (what > 85 % of the README run's steps do)
     n_steps = cf.n_past + cf.n_future - 1
@@ -348,7 +399,7 @@ def bench_train(args, dev, rank, world, distributed, exact_of=None):
     barrier_sync(distributed)
     t0 = time.perf_counter()
     for i in range(steps):
-        tr._train_step(batches_dev[i % 2], use_truth=use_truth)
+        losses = tr._train_step(batches_dev[i % 2], use_truth=use_truth)
     barrier_sync(distributed)
     dt_local = time.perf_counter() - t0
     opt = tr.optimizer
@@ -358,6 +409,7 @@ def bench_train(args, dev, rank, world, distributed, exact_of=None):
     opt.wait_params()  # nothing of this trainer's optimiser stays installed behind it (ops.PARAM_GATE is process-global)
     if ops.PARAM_GATE is opt:
         ops.PARAM_GATE = None
+    outputs = {"losses": dict(losses), "state": state_sample(tr.model)} if dump else None
     dt = max_over_ranks(dt_local, dev, distributed)
     log(f"train{'' if exact_of is None else ' (exact fp32)'}: {steps} steps in {dt:.3f} s")
     ops.PROFILE = None
@@ -382,7 +434,7 @@ def bench_train(args, dev, rank, world, distributed, exact_of=None):
             "step_tflops_per_gpu": step_flop / (dt / steps) / 1e12, "step_tflop": step_flop / 1e12, "kernel": kern,
             "global_batch": world * B, "phases": phase_breakdown(events, steps), "steps": steps,
             "rank_ms_per_step": [x / steps * 1e3 for x in per_rank(dt_local, dev, distributed, world)],
-            "check": check, "cf": cf, "workload": train_workload_name(args, cf), "optimizer": opt_info}
+            "check": check, "cf": cf, "workload": train_workload_name(args, cf), "optimizer": opt_info, "outputs": outputs}
 
 
 def side_only(args, name):
@@ -403,7 +455,7 @@ class SyntheticRobotInputs:
         return self.model.predict_batch(data, thick)
 
 
-def bench_cem(args, dev, rank, world, distributed, ra=False, exact_of=None, deployed=False):
+def bench_cem(args, dev, rank, world, distributed, ra=False, exact_of=None, deployed=False, dump=False):
     """`ra`: the robot-aware planner (mask + future mask + robot state into the model, dontcare cost; per-candidate
     states / masks produced on the device).  `exact_of`: repeat the split-precision run's problem with the same weights
     on the exact-fp32 MFMA kernels (one timed iteration).  `deployed`: the reference's deployed checkpoints' model
@@ -484,11 +536,12 @@ def bench_cem(args, dev, rank, world, distributed, ra=False, exact_of=None, depl
            "rank_s_per_iter": [x / iters for x in per_rank(dt_local, dev, distributed, world)],
            "cost_allgather_ms": float(np.mean(gather_s)) * 1e3 if distributed else None, "get_action": None}
     out["gflop_per_candidate_step"] = per_fwd
+    out["outputs"] = {"sum_cost": np.array(ro["sum_cost"], np.float64)} if dump else None
     if exact_of is not None:
         if exact_of["check"] is not None:
             out["check_sum_cost"] = ro["sum_cost"][exact_of["check"]["idx"]].copy()
         return out
-    if deployed:
+    if deployed or not getattr(args, "full", False):
         return out
     # secondary metric: the whole planner call at the config's opt_iter -- sampling, robot inputs, rollouts,
     # cost gather, top-k, refit
@@ -688,10 +741,18 @@ def main():
                          "(all) or every other one (mix); not the headline")
     ap.add_argument("--group-norm", action="store_true",
                     help="both workloads with --lstm_group_norm True (NormConvLSTMCell; not the headline config)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the cem workloads with --workload both, the planner's get_action, "
+                         "the side lines, the exact-fp32 runs, both gradient-exchange modes (N > 1) and the CPU baseline "
+                         "with its oracle checks (N = 1); a plain run times the headline workload alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed paths computed in their last step as DIR/<name>.npy")
     args = ap.parse_args()
+    full = args.full
+    dump = args.dump_outputs is not None and rank_of_env() == 0
 
     world = int(os.environ.get("WORLD_SIZE", 1))
-    rank = int(os.environ.get("RANK", 0))
+    rank = rank_of_env()
     local = int(os.environ.get("LOCAL_RANK", 0))
     # (RAC_DIST_FORCE=1: a one-rank process group -- every collective of the path runs through RCCL on a one-GPU box)
     distributed = world > 1 or os.environ.get("RAC_DIST_FORCE", "0") == "1"
@@ -731,14 +792,14 @@ def main():
 
     out = {"metric": "SVG train frames/sec + CEM candidate-rollouts/sec, 64x64", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "higher_is_better": True, "scaling": "weak",
-           "vs_baseline": None, "data": "synthetic",
+           "vs_baseline": None, "data": "synthetic", "full": full,
            "dtype": "fp32 (conv operands as two fp16 parts = 22 significant bits, fp32 accumulate; see fp32_exact)"}
     train = cem = None
     ddp_modes = None
     if args.workload in ("both", "train"):
-        train = bench_train(args, dev, rank, world, distributed)
+        train = bench_train(args, dev, rank, world, distributed, dump=dump)
         torch.cuda.empty_cache()
-        if distributed and not args.no_ddp_modes:
+        if distributed and full and not args.no_ddp_modes:
             # both gradient-exchange designs on the same ranks, same workload: all-reduce + the full fused Adam on every
             # rank, and reduce-scatter + Adam on 1/N slices + parameter all-gather.  The headline is the mode
             # the flags chose (all-reduce unless --shard-optimizer); a failure of the other mode is recorded, not fatal.
@@ -774,15 +835,15 @@ def main():
                 os._exit(3)
             torch.cuda.empty_cache()
     cem_ra = None
-    if args.workload in ("both", "cem"):
-        cem = bench_cem(args, dev, rank, world, distributed, deployed=args.deployed)
+    if args.workload == "cem" or (args.workload == "both" and full):
+        cem = bench_cem(args, dev, rank, world, distributed, deployed=args.deployed, dump=dump)
         torch.cuda.empty_cache()
-        if not args.no_cem_ra and not args.group_norm and not args.deployed:
-            cem_ra = bench_cem(args, dev, rank, world, distributed, ra=True)
+        if full and not args.no_cem_ra and not args.group_norm and not args.deployed:
+            cem_ra = bench_cem(args, dev, rank, world, distributed, ra=True, dump=dump)
             torch.cuda.empty_cache()
     side = None
     headline = not (args.h48 or args.cfg5 or args.group_norm or args.deployed or args.sched)
-    if train is not None and not args.no_side and headline:
+    if train is not None and full and not args.no_side and headline:
         # BASELINE configs[4] per GPU (128x128 frames, bs 8, n_future 10: the shard one of 8 DDP ranks trains on), driver-timed
         sa = argparse.Namespace(**vars(args))
         sa.cfg5, sa.steps, sa.warmup = True, args.side_steps, 2
@@ -796,7 +857,7 @@ def main():
                          "step_achieved": st["step_tflops_per_gpu"], "step_peak": SPLIT_PEAK_TFLOPS,
                          "step_frac": st["step_tflops_per_gpu"] / SPLIT_PEAK_TFLOPS,
                          "time_breakdown_ms": st["phases"]}}
-    if train is not None and not args.no_side and headline:
+    if train is not None and full and not args.no_side and headline:
         # the paths the reference's own command lines take (README.md:103,111: --scheduled_sampling True;
         # evaluate_checkpoint.py:40-46: --lstm_group_norm True, g 256; config/__init__.py:165-171: 48 x 64 frames)
         def train_side(**switches):
@@ -819,7 +880,7 @@ def main():
         side["sched_mix"]["vs_teacher_forced"] = side["sched_mix"]["ms_per_step"] / train["ms_per_step"]
         side["deployed_train"] = train_side(deployed=True)
         side["deployed_train_sched"] = train_side(deployed=True, sched="all")
-    if cem is not None and not args.no_side and headline:
+    if cem is not None and full and not args.no_side and headline:
         dc = bench_cem(args, dev, rank, world, distributed, deployed=True)
         torch.cuda.empty_cache()
         side = side or {}
@@ -834,7 +895,7 @@ def main():
                                 "achieved_tflops_per_gpu": dc["tflops_per_gpu"],
                                 "frac_of_split_peak": dc["tflops_per_gpu"] / SPLIT_PEAK_TFLOPS}
     exact = arith_err = None
-    if not args.no_exact and headline:
+    if full and not args.no_exact and headline:
         exact, arith_err = exact_fp32_runs(args, dev, rank, world, distributed, train, cem)
 
     if train is not None:
@@ -937,7 +998,7 @@ def main():
         out["fp32_exact"] = exact
     if distributed and "dist" not in out:
         out["dist"] = dist_info
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(train, cem)
         if cem_ra is not None and cem_ra["check"] is not None:
             cb.setdefault("checked", {}).update(check_cem_ra(cem_ra))  # (the robot-aware line's own check)
@@ -961,6 +1022,8 @@ def main():
         arith_err["note"] = ("max relative error: train = the first optimiser step's loss terms, cem = sum_cost of the 64 "
                              "checked candidates (relative to the largest)")
         out["arith_error"] = arith_err
+    if dump:
+        write_outputs(args.dump_outputs, train, cem, cem_ra)
     if rank == 0:
         print(json.dumps(out))
     if distributed:

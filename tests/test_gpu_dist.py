@@ -206,7 +206,8 @@ def test_bench_two_ranks_rehearsal():
     """Plain `python bench.py --gpus 2` end to end (no WORLD_SIZE in the environment: the script starts its own ranks as a
     child torch.distributed.run before it touches the GPU -- the same launch the driver's explicit torchrun command ends
     in), before an 8-GPU node ever runs it: both ranks share this box's one MI355X and gloo stands in for RCCL
-    (RAC_BENCH_ONE_GPU / RAC_DIST_BACKEND, the script's own rehearsal switches).  Both gradient-exchange modes are timed."""
+    (RAC_BENCH_ONE_GPU / RAC_DIST_BACKEND, the script's own rehearsal switches).  Both gradient-exchange modes are timed
+    (--full: a plain run times the headline alone)."""
     import json
     import subprocess
     import sys
@@ -218,7 +219,7 @@ def test_bench_two_ranks_rehearsal():
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
            "--warmup", "1", "--cem-candidates", "64", "--cem-batch", "64", "--cem-iters", "1", "--cem-opt-iter", "2",
-           "--no-exact", "--no-side"]  # (the exact-fp32 and configs[4] legs: rank-agnostic, rehearsed in test_gpu_nccl.py)
+           "--no-exact", "--no-side", "--full"]  # (the exact-fp32 and configs[4] legs: rank-agnostic, rehearsed in test_gpu_nccl.py)
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

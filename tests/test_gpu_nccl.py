@@ -61,7 +61,7 @@ def test_bench_under_torchrun_one_rank_rccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
            "--warmup", "1", "--cem-candidates", "64", "--cem-batch", "64", "--cem-iters", "1", "--cem-opt-iter", "2",
-           "--exact-steps", "1", "--side-steps", "1", "--no-cem-ra", "--no-cpu-baseline"]
+           "--exact-steps", "1", "--side-steps", "1", "--no-cem-ra", "--no-cpu-baseline", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=_env(RAC_DIST_FORCE="1"), capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
