@@ -337,9 +337,11 @@ int rac_lstm_cell_bwd(const float* dh, const float* dc_next, const float* act, c
 /* The whole cell behind its two gate convs, without a tape (the frozen model: planner rollouts, evaluation), in ONE launch:
  *   gates = GroupNorm(16, 4g)(g_ih) + GroupNorm(16, 4g)(g_hh);  i, f, o = sigmoid, g~ = tanh  (chunk order i, f, o, g~)
  *   c = GroupNorm(16, g)(f * c_prev + i * g~);  h = o * tanh(c)                                (lstm.py:174-198)
- * g_ih / g_hh = the convs' outputs incl. bias, [B][HW][4g]; c_prev, h, c = [B][HW][g]; g = 16 * 2^k; 16-byte aligned.
- * One workgroup per (image, quarter of the channels): an image's result does not depend on the batch.
- * Training (all five or none): act [B][HW][4g] = the activated gates, c_raw [B][HW][g] = the cell before its norm, stat_ih /
+ * g_ih / g_hh = the convs' outputs incl. bias, [B][HW][4g]; c_prev, h, c = [B][HW][g]; g = 64 * 2^k <= 4096 (a cell
+ * group, g / 16 channels, is whole 16-byte vectors; any other g is refused); 16-byte aligned.
+ * One workgroup per (image, quarter of the channels): an image's result does not depend on the batch (the same bits in
+ * any batch: the launch geometry of this form ignores B).
+ * Training (all five or none; the workgroup size then follows B, so across batch sizes the sums may run in another order): act [B][HW][4g] = the activated gates, c_raw [B][HW][g] = the cell before its norm, stat_ih /
  * stat_hh / stat_c [2][B][16] = mean and 1 / std of every (image, group) -- the operands of rac_lstm_out_bwd,
  * rac_groupnorm_bwd and rac_lstm_core_bwd. */
 int rac_norm_lstm_cell_fwd(const float* g_ih, const float* g_hh, const float* c_prev, const float* gamma_ih,
@@ -348,7 +350,8 @@ int rac_norm_lstm_cell_fwd(const float* g_ih, const float* g_hh, const float* c_
                            float* stat_c, int32_t B, int32_t HW, int32_t g, float eps, void* stream);
 /* The adjoint of rac_norm_lstm_cell_fwd in ONE launch: from dh and dc (gradients of h and of the normalised cell; either
  * may be NULL) and the forward pass's act / c / c_raw / stats to dg_ih, dg_hh (gradients of the two gate convs' outputs,
- * their max |.| folded into the two slots), dc_prev, and -- all six or none -- the three norms' affine gradients (+=). */
+ * their max |.| folded into the two slots), dc_prev, and -- all six or none -- the three norms' affine gradients (+=).
+ * The same widths as rac_norm_lstm_cell_fwd. */
 int rac_norm_lstm_cell_bwd(const float* dh, const float* dc, const float* act, const float* c, const float* c_raw,
                            const float* c_prev, const float* g_ih, const float* g_hh, const float* stat_ih,
                            const float* stat_hh, const float* stat_c, const float* gamma_ih, const float* gamma_hh,

@@ -1684,7 +1684,8 @@ __global__ void groupnorm_fwd_kernel(const float* x, const float* gamma, const f
 // 4 + q, 8 + q, 12 + q of both convs (gate k of channel c is channel k g + c: group 4 k + q) and cell groups 4 q .. 4 q + 3,
 // all of them whole.  grid (4, B), 256 threads: one (image, quarter) per workgroup, its 8 + 1 slabs of HW x g/4 values read
 // three times (mean; centred squares, as groupnorm_fwd_kernel; gates) -- the first time from memory, then from the caches.
-// An image's arithmetic touches nothing of another image: batch-invariant by construction.
+// An image's arithmetic touches nothing of another image, and the frozen form's thread count does not depend on the batch:
+// batch-invariant to the bit.
 __global__ __launch_bounds__(512) void norm_lstm_cell_fwd_kernel(const float* g_ih, const float* g_hh, const float* c_prev,
                                                                  const float* gam_ih, const float* bet_ih,
                                                                  const float* gam_hh, const float* bet_hh,
@@ -1695,7 +1696,7 @@ __global__ __launch_bounds__(512) void norm_lstm_cell_fwd_kernel(const float* g_
   // (training: act_out [B][HW][4g] = the activated gates, craw_out = the cell before its norm, stat_* [2][B][16] = mean and
   // 1 / std of every (image, group) -- what rac_lstm_out_bwd / rac_groupnorm_bwd / rac_lstm_core_bwd read; NULL: the frozen model)
   __shared__ float red[8][12];
-  const int NT = blockDim.x, NW = NT >> 6;  // 256 threads, or 512 for small batches (few workgroups: more loads in flight each)
+  const int NT = blockDim.x, NW = NT >> 6;  // 256 threads, or 512 for small training batches (few workgroups: more loads in flight each)
   const int q = blockIdx.x, b = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int Cq = g >> 2, Q4 = Cq >> 2;          // channels of the quarter, 16-byte vectors per pixel of it
@@ -1763,8 +1764,8 @@ __global__ __launch_bounds__(512) void norm_lstm_cell_fwd_kernel(const float* g_
       stat_hh[b * 16 + 4 * k + q] = mean[4 + k], stat_hh[(nB + b) * 16 + 4 * k + q] = rstd[4 + k];
     }
   }
-  // gates and the raw cell; the quarter's four cell groups: a thread's vectors all lie in ONE group when Q4 divides 256
-  // or 256 divides Q4's multiples -- the launcher's condition (Q4 a power of two <= 256), so one accumulator serves
+  // gates and the raw cell; the quarter's four cell groups hold g / 16 channels each: whole 16-byte vectors, so a vector
+  // lies in ONE group (4 c4) / cg -- the launcher's condition g % 64 == 0
   const float* cp = c_prev + (long)b * HW * g + q * Cq;
   float* co = c_out + (long)b * HW * g + q * Cq;
   float* ho = h_out + (long)b * HW * g + q * Cq;
@@ -2174,11 +2175,14 @@ int rac_groupnorm_fwd(const float* x, const float* gamma, const float* beta, flo
   return check_launch("rac_groupnorm_fwd");
 }
 
-// threads per (image, quarter) workgroup of the fused NormConvLSTMCell kernels: 512 while the launch has fewer workgroups
-// than two per CU (a training batch: 64) -- the passes are bound by what one workgroup keeps in flight -- else 256
-static int norm_cell_threads(int B, int g) {
+// threads per (image, quarter) workgroup of the fused NormConvLSTMCell kernels.  Training: 512 while the launch has fewer
+// workgroups than two per CU (a training batch: 64) -- the passes are bound by what one workgroup keeps in flight -- else
+// 256.  The frozen form (no tape) never looks at B: the thread count sets each thread's stride and the order of the
+// cross-wave sums, so an image's bits would change with the batch it sits in -- 256, what every batch >= 128 took anyway.
+static int norm_cell_threads(int B, int g, bool frozen) {
   static const int forced = [] { const char* e = getenv("RAC_NORM_CELL_THREADS"); return e ? atoi(e) : 0; }();
   if (forced == 256 || forced == 512) return forced;
+  if (frozen) return 256;
   return (4 * B < 512 && g / 16 <= 256) ? 512 : 256;
 }
 
@@ -2194,12 +2198,12 @@ int rac_norm_lstm_cell_fwd(const float* g_ih, const float* g_hh, const float* c_
                   (!act || (aligned16(act) && aligned16(c_raw))),
               "rac_norm_lstm_cell_fwd: act / c_raw / stat_ih / stat_hh / stat_c come together (training) or not at all");
   const int Q4 = g / 16;
-  RAC_REQUIRE(g % 16 == 0 && Q4 >= 1 && Q4 <= 256 && (Q4 & (Q4 - 1)) == 0 && B <= 65535,
-              "rac_norm_lstm_cell_fwd: g must be 16 * 2^k <= 4096 (GroupNorm(16, .) groups of whole 16-byte vectors)");
+  RAC_REQUIRE(g % 64 == 0 && Q4 <= 256 && (Q4 & (Q4 - 1)) == 0 && B <= 65535,
+              "rac_norm_lstm_cell_fwd: g must be 64 * 2^k <= 4096 (GroupNorm(16, g) groups of whole 16-byte vectors)");
   RAC_REQUIRE(aligned16(g_ih) && aligned16(g_hh) && aligned16(c_prev) && aligned16(h) && aligned16(c) && aligned16(gamma_ih) &&
                   aligned16(beta_ih) && aligned16(gamma_hh) && aligned16(beta_hh) && aligned16(gamma_c) && aligned16(beta_c),
               "rac_norm_lstm_cell_fwd: 16-byte aligned operands");
-  hipLaunchKernelGGL(norm_lstm_cell_fwd_kernel, dim3(4, B), dim3(norm_cell_threads(B, g)), 0, ST(stream), g_ih, g_hh, c_prev, gamma_ih, beta_ih,
+  hipLaunchKernelGGL(norm_lstm_cell_fwd_kernel, dim3(4, B), dim3(norm_cell_threads(B, g, act == nullptr)), 0, ST(stream), g_ih, g_hh, c_prev, gamma_ih, beta_ih,
                      gamma_hh, beta_hh, gamma_c, beta_c, h, c, act, c_raw, stat_ih, stat_hh, stat_c, HW, g, eps);
   return check_launch("rac_norm_lstm_cell_fwd");
 }
@@ -2214,8 +2218,8 @@ int rac_norm_lstm_cell_bwd(const float* dh, const float* dc, const float* act, c
                   dg_ih && dg_hh && dc_prev && B > 0 && HW > 0 && g > 0,
               "rac_norm_lstm_cell_bwd: bad args");
   const int Q4 = g / 16;
-  RAC_REQUIRE(g % 16 == 0 && Q4 >= 1 && Q4 <= 256 && (Q4 & (Q4 - 1)) == 0 && B <= 65535,
-              "rac_norm_lstm_cell_bwd: g must be 16 * 2^k <= 4096");
+  RAC_REQUIRE(g % 64 == 0 && Q4 <= 256 && (Q4 & (Q4 - 1)) == 0 && B <= 65535,
+              "rac_norm_lstm_cell_bwd: g must be 64 * 2^k <= 4096 (GroupNorm(16, g) groups of whole 16-byte vectors)");
   const bool aff = dgamma_ih != nullptr;
   RAC_REQUIRE(aff == (dbeta_ih != nullptr) && aff == (dgamma_hh != nullptr) && aff == (dbeta_hh != nullptr) &&
                   aff == (dgamma_c != nullptr) && aff == (dbeta_c != nullptr),
@@ -2224,7 +2228,7 @@ int rac_norm_lstm_cell_bwd(const float* dh, const float* dc, const float* act, c
                   aligned16(c_prev) && aligned16(g_ih) && aligned16(g_hh) && aligned16(dg_ih) && aligned16(dg_hh) &&
                   aligned16(dc_prev) && aligned16(gamma_ih) && aligned16(gamma_hh) && aligned16(gamma_c),
               "rac_norm_lstm_cell_bwd: 16-byte aligned operands");
-  const int nt = norm_cell_threads(B, g);
+  const int nt = norm_cell_threads(B, g, false);
   const size_t lds = aff ? (size_t)14 * nt * 16 : 0;  // (57 / 115 KB: the one meeting of the per-thread affine sums)
   static bool attr = false;
   if (!attr) {

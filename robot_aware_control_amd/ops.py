@@ -2551,7 +2551,9 @@ NORM_CELL_FUSED = os.environ.get("RAC_NORM_CELL_FUSED", "1") == "1"  # the froze
 
 
 def norm_cell_frozen_ok(g: int) -> bool:
-    return NORM_CELL_FUSED and g % 16 == 0 and (g // 16) & (g // 16 - 1) == 0 and g <= 4096
+    """Widths the fused cell kernels take (rac_norm_lstm_cell_fwd / _bwd check the same): g = 64 * 2^k <= 4096 -- a
+    GroupNorm(16, g) group of the cell is then whole 16-byte vectors.  Other widths run the unfused kernels."""
+    return NORM_CELL_FUSED and g >= 64 and g % 64 == 0 and g & (g - 1) == 0 and g <= 4096
 
 
 def norm_cell_frozen(g_ih, g_hh, c_prev, gn_ih, gn_hh, gn_c):

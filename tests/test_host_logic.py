@@ -188,3 +188,17 @@ def test_bench_starts_its_own_ranks(monkeypatch):
     monkeypatch.setenv("WORLD_SIZE", "4")
     bench._launch_ranks_if_needed()  # launched by torch.distributed.run: a rank
     assert not calls
+
+
+def test_fused_norm_cell_width_predicate(monkeypatch):
+    """ops.norm_cell_frozen_ok -- the gate of the fused NormConvLSTMCell kernels in model.py, and through
+    ops.norm_cell_node_ok of the one-node training form -- admits exactly g = 64 * 2^k <= 4096: in a narrower cell a
+    GroupNorm(16, g) group is less than one 16-byte vector, which the kernels assign to a single group.  (That both
+    launchers refuse the same widths is checked on the device: tests/test_gpu_norm_cell.py.)"""
+    from robot_aware_control_amd import ops
+    monkeypatch.setattr(ops, "NORM_CELL_FUSED", True)
+    admitted = [g for g in range(1, 8193) if ops.norm_cell_frozen_ok(g)]
+    assert admitted == [64, 128, 256, 512, 1024, 2048, 4096]
+    assert not ops.norm_cell_frozen_ok(0)
+    monkeypatch.setattr(ops, "NORM_CELL_FUSED", False)
+    assert not any(ops.norm_cell_frozen_ok(g) for g in (64, 256, 4096))
