@@ -557,6 +557,35 @@ typedef struct rac_adam_range {
 int rac_adam_ranges(float* p, const float* g, float* m, float* v, const rac_adam_range* ranges, int32_t n_ranges,
                     int64_t total_blocks, float lr, float beta1, float beta2, float eps, int32_t step, void* stream);
 
+/* torch.optim.RMSprop (centered = False) and torch.optim.SGD steps (trainer.py:111-116), weight_decay = 0, fused over
+ * flat buffers with torch's arithmetic and association:
+ *   RAC_OPTIM_RMSPROP  state0 = square_avg, state1 = momentum_buffer (read only when momentum > 0, else may be NULL)
+ *       sq = alpha sq + gain g g   (gain = 1 - alpha);   avg = sqrt(sq) + eps
+ *       momentum == 0:  p += (-lr g) / avg          momentum > 0:  buf = momentum buf + g / avg;  p += -lr buf
+ *   RAC_OPTIM_SGD      state0 = momentum_buffer (read only when momentum != 0, else may be NULL), state1 unused
+ *       momentum == 0:  p += -lr g
+ *       momentum != 0:  buf = g on RAC_OPTIM_FIRST_STEP, else momentum buf + gain g   (gain = 1 - dampening);
+ *                       p += -lr buf,  or  p += -lr (g + momentum buf) with RAC_OPTIM_NESTEROV
+ * `gain` is handed over rounded once from double, as torch rounds `1 - alpha` / `1 - dampening`; alpha and eps are
+ * ignored by SGD.  Both entry points share one rule function per optimiser: an element gets the same bits whichever
+ * updates it.  16-byte aligned buffers. */
+enum { RAC_OPTIM_RMSPROP = 0, RAC_OPTIM_SGD = 1 };
+enum { RAC_OPTIM_NESTEROV = 1, RAC_OPTIM_FIRST_STEP = 2 }; /* flags word */
+int rac_optim_step(float* p, const float* g, float* state0, float* state1, int64_t n, int32_t rule, int32_t flags,
+                   float lr, float momentum, float gain, float alpha, float eps, void* stream);
+/* The same step over a list of float4 ranges [begin4, begin4 + n4) of the flat buffers (device table; range r owns the
+ * workgroups [block_begin_r, block_begin_{r+1}), ceil(n4 / 1024) each).  A range with a non-NULL `amax` also folds
+ * bits(max |p_new|) over the range into that slot (zero or an earlier maximum on entry; NULL: no maximum wanted): one
+ * launch updates a whole flat buffer and leaves the exact new maximum of every split-precision conv weight in it, ready
+ * for rac_weight_frag_split_multi -- no rac_absmax_multi pass over the updated weights. */
+typedef struct rac_optim_range {
+  int64_t begin4, n4, block_begin;
+  uint32_t* amax; /* or NULL */
+} rac_optim_range;
+int rac_optim_ranges(float* p, const float* g, float* state0, float* state1, const rac_optim_range* ranges,
+                     int32_t n_ranges, int64_t total_blocks, int32_t rule, int32_t flags, float lr, float momentum,
+                     float gain, float alpha, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,15 @@ class AdamRange(C.Structure):
     _fields_ = [("begin4", i64), ("n4", i64), ("block_begin", i64)]
 
 
+class OptimRange(C.Structure):
+    """struct rac_optim_range (include/rac_hip.h)."""
+    _fields_ = [("begin4", i64), ("n4", i64), ("block_begin", i64), ("amax", vp)]
+
+
+OPTIM_RMSPROP, OPTIM_SGD = 0, 1            # RAC_OPTIM_* rules
+OPTIM_NESTEROV, OPTIM_FIRST_STEP = 1, 2    # RAC_OPTIM_* flags
+
+
 class GradSrc(C.Structure):
     """struct rac_grad_src (include/rac_hip.h): one addend of a gradient map, slabs read through a column window."""
     _fields_ = [("p", vp), ("slab_stride", i64), ("n_slabs", i32), ("row_stride", i32), ("col_off", i32),
@@ -154,6 +163,8 @@ _SIGS = {
     "rac_adam_frag_multi_bounded": [vp, i32, i64, i32, f32, f32, f32, f32, i32, vp],
     "rac_amax_bound": [vp, vp, vp, i32, f32, vp],
     "rac_adam_ranges": [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, i32, vp],
+    "rac_optim_step": [vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, f32, vp],
+    "rac_optim_ranges": [vp, vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, f32, f32, f32, vp],
     "rac_version": [],
     "rac_device_arch": [],
     "rac_last_error": [],

@@ -71,6 +71,33 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
   p = p - step_size * (m / denom);
 }
 
+// One RMSprop / SGD update (torch.optim semantics and association, reference trainer.py:111-116; include/rac_hip.h
+// rac_optim_step), shared by optim_kernel and optim_ranges_kernel with floating-point contraction OFF: the same bits
+// whichever kernel updates an element.  gain = 1 - alpha / 1 - dampening, neg_lr = -lr; `buf` is touched only when
+// momentum != 0 (the callers pass a dummy otherwise).
+__device__ __forceinline__ void rmsprop_update(float& p, float g, float& sq, float& buf, float neg_lr, float momentum,
+                                               float gain, float alpha, float eps) {
+#pragma clang fp contract(off)
+  sq = alpha * sq + (gain * g) * g;
+  const float avg = sqrtf(sq) + eps;
+  if (momentum > 0.f) {
+    buf = momentum * buf + g / avg;
+    p = p + neg_lr * buf;
+  } else {
+    p = p + (neg_lr * g) / avg;
+  }
+}
+__device__ __forceinline__ void sgd_update(float& p, float g, float& buf, float neg_lr, float momentum, float gain,
+                                           bool nesterov, bool first_step) {
+#pragma clang fp contract(off)
+  float d = g;
+  if (momentum != 0.f) {
+    buf = first_step ? g : momentum * buf + gain * g;
+    d = nesterov ? g + momentum * buf : buf;
+  }
+  p = p + neg_lr * d;
+}
+
 // max |v| bookkeeping for the split-precision convs (include/rac_hip.h, rac_absmax): a kernel that produces a
 // tensor folds the bit pattern of its max |v| into a device slot -- wave reduce, then at most one atomic per wave and
 // only if it can raise the slot.  Every lane of the wave must call amax_commit.

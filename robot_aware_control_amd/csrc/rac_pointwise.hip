@@ -1097,6 +1097,76 @@ __global__ void adam_ranges_kernel(f32x4* p, const f32x4* g, f32x4* m, f32x4* v,
   }
 }
 
+// ------------------------------------------------------------- RMSprop / SGD
+struct OptimArgs {
+  float neg_lr, momentum, gain, alpha, eps;
+  int flags;
+};
+
+// RULE: RAC_OPTIM_*; MOM: the momentum buffer exists (RMSprop: state1, SGD: state0) -- a buffer a rule does not have is
+// never dereferenced.
+template <int RULE, bool MOM>
+__device__ __forceinline__ void optim_update1(float& p, float g, float& s0, float& s1, const OptimArgs& a) {
+  if (RULE == RAC_OPTIM_RMSPROP)
+    rmsprop_update(p, g, s0, s1, a.neg_lr, MOM ? a.momentum : 0.f, a.gain, a.alpha, a.eps);
+  else
+    sgd_update(p, g, s0, a.neg_lr, MOM ? a.momentum : 0.f, a.gain, (a.flags & RAC_OPTIM_NESTEROV) != 0,
+               (a.flags & RAC_OPTIM_FIRST_STEP) != 0);
+}
+
+// one float4 of the flat buffers; returns the bit pattern of max |p_new| over its four elements
+template <int RULE, bool MOM>
+__device__ __forceinline__ unsigned optim_update4(f32x4* p, const f32x4* g, f32x4* s0, f32x4* s1, long i, const OptimArgs& a) {
+  constexpr bool HAS0 = RULE == RAC_OPTIM_RMSPROP || MOM, HAS1 = RULE == RAC_OPTIM_RMSPROP && MOM;
+  f32x4 P = p[i], S0 = {0.f, 0.f, 0.f, 0.f}, S1 = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 G = g[i];
+  if (HAS0) S0 = s0[i];
+  if (HAS1) S1 = s1[i];
+  unsigned mx = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float pe = P[e], a0 = S0[e], a1 = S1[e];
+    optim_update1<RULE, MOM>(pe, G[e], a0, a1, a);
+    P[e] = pe, S0[e] = a0, S1[e] = a1;
+    mx = max(mx, absbits(pe));
+  }
+  p[i] = P;
+  if (HAS0) s0[i] = S0;
+  if (HAS1) s1[i] = S1;
+  return mx;
+}
+
+template <int RULE, bool MOM>
+__global__ void optim_kernel(f32x4* p, const f32x4* g, f32x4* s0, f32x4* s1, long n4, float* pt, const float* gt, float* s0t,
+                             float* s1t, int tail, OptimArgs a) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
+    optim_update4<RULE, MOM>(p, g, s0, s1, i, a);
+  if (blockIdx.x == 0 && threadIdx.x < tail) {
+    constexpr bool HAS0 = RULE == RAC_OPTIM_RMSPROP || MOM, HAS1 = RULE == RAC_OPTIM_RMSPROP && MOM;
+    float a0 = HAS0 ? s0t[threadIdx.x] : 0.f, a1 = HAS1 ? s1t[threadIdx.x] : 0.f;
+    optim_update1<RULE, MOM>(pt[threadIdx.x], gt[threadIdx.x], a0, a1, a);
+    if (HAS0) s0t[threadIdx.x] = a0;
+    if (HAS1) s1t[threadIdx.x] = a1;
+  }
+}
+
+// The same update over a device table of float4 ranges (as adam_ranges_kernel: a workgroup per 1024 float4); a range with
+// an amax slot also gets bits(max |p_new|) folded into it -- one conditional atomic per workgroup.
+template <int RULE, bool MOM>
+__global__ void optim_ranges_kernel(f32x4* p, const f32x4* g, f32x4* s0, f32x4* s1, const rac_optim_range* ranges,
+                                    int n_ranges, OptimArgs a) {
+  int lo = 0, hi = n_ranges - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (ranges[mid].block_begin <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  const rac_optim_range r = ranges[lo];
+  const long first = r.begin4 + (blockIdx.x - r.block_begin) * 1024L, last = min(r.begin4 + r.n4, first + 1024L);
+  unsigned mx = 0;
+  for (long i = first + threadIdx.x; i < last; i += blockDim.x) mx = max(mx, optim_update4<RULE, MOM>(p, g, s0, s1, i, a));
+  if (r.amax) amax_commit_block(mx, r.amax);  // (uniform over the workgroup: every thread calls it or none does)
+}
+
 }  // namespace rac
 
 using namespace rac;
@@ -1634,6 +1704,59 @@ int rac_adam_ranges(float* p, const float* g, float* m, float* v, const rac_adam
                      (float)(1.0 / sqrt(bc2)));
   return check_launch("rac_adam_ranges");
 }
+
+// which of the four kernel forms a (rule, momentum) pair takes, after the argument checks both entry points share
+static int optim_form(const char* who, const float* p, const float* g, const float* state0, const float* state1, int32_t rule,
+                      int32_t flags, float momentum, bool* mom) {
+  RAC_REQUIRE(p && g && (rule == RAC_OPTIM_RMSPROP || rule == RAC_OPTIM_SGD), "%s: bad args", who);
+  RAC_REQUIRE((flags & ~(RAC_OPTIM_NESTEROV | RAC_OPTIM_FIRST_STEP)) == 0, "%s: unknown flags 0x%x", who, flags);
+  RAC_REQUIRE(momentum >= 0.f, "%s: momentum must be >= 0", who);
+  *mom = momentum > 0.f;
+  const float* buf = rule == RAC_OPTIM_RMSPROP ? state1 : state0;
+  RAC_REQUIRE(rule != RAC_OPTIM_RMSPROP || state0, "%s: RMSprop needs state0 (square_avg)", who);
+  RAC_REQUIRE(!*mom || buf, "%s: momentum > 0 needs the momentum buffer", who);
+  RAC_REQUIRE(aligned16(p) && aligned16(g) && aligned16(state0) && aligned16(state1), "%s: buffers must be 16-B aligned", who);
+  return RAC_OK;
+}
+
+#define RAC_OPTIM_DISPATCH(KERNEL, rule, mom, ...)                                       \
+  do {                                                                                   \
+    if ((rule) == RAC_OPTIM_RMSPROP) {                                                   \
+      if (mom) hipLaunchKernelGGL((KERNEL<RAC_OPTIM_RMSPROP, true>), __VA_ARGS__);       \
+      else hipLaunchKernelGGL((KERNEL<RAC_OPTIM_RMSPROP, false>), __VA_ARGS__);          \
+    } else {                                                                             \
+      if (mom) hipLaunchKernelGGL((KERNEL<RAC_OPTIM_SGD, true>), __VA_ARGS__);           \
+      else hipLaunchKernelGGL((KERNEL<RAC_OPTIM_SGD, false>), __VA_ARGS__);              \
+    }                                                                                    \
+  } while (0)
+
+int rac_optim_step(float* p, const float* g, float* state0, float* state1, int64_t n, int32_t rule, int32_t flags,
+                   float lr, float momentum, float gain, float alpha, float eps, void* stream) {
+  bool mom;
+  if (int e = optim_form("rac_optim_step", p, g, state0, state1, rule, flags, momentum, &mom)) return e;
+  RAC_REQUIRE(n > 0, "rac_optim_step: bad args");
+  const OptimArgs a = {-lr, momentum, gain, alpha, eps, flags};
+  const long n4 = n / 4;
+  const int tail = (int)(n - n4 * 4);
+  float* s0t = state0 ? state0 + n4 * 4 : nullptr;
+  float* s1t = state1 ? state1 + n4 * 4 : nullptr;
+  RAC_OPTIM_DISPATCH(optim_kernel, rule, mom, dim3(grid_for(n4 > 0 ? n4 : 1)), dim3(256), 0, ST(stream), (f32x4*)p,
+                     (const f32x4*)g, (f32x4*)state0, (f32x4*)state1, n4, p + n4 * 4, g + n4 * 4, s0t, s1t, tail, a);
+  return check_launch("rac_optim_step");
+}
+
+int rac_optim_ranges(float* p, const float* g, float* state0, float* state1, const rac_optim_range* ranges,
+                     int32_t n_ranges, int64_t total_blocks, int32_t rule, int32_t flags, float lr, float momentum,
+                     float gain, float alpha, float eps, void* stream) {
+  bool mom;
+  if (int e = optim_form("rac_optim_ranges", p, g, state0, state1, rule, flags, momentum, &mom)) return e;
+  RAC_REQUIRE(ranges && n_ranges > 0 && total_blocks >= n_ranges && total_blocks < 0x7FFFFFFFL, "rac_optim_ranges: bad args");
+  const OptimArgs a = {-lr, momentum, gain, alpha, eps, flags};
+  RAC_OPTIM_DISPATCH(optim_ranges_kernel, rule, mom, dim3((unsigned)total_blocks), dim3(256), 0, ST(stream), (f32x4*)p,
+                     (const f32x4*)g, (f32x4*)state0, (f32x4*)state1, ranges, n_ranges, a);
+  return check_launch("rac_optim_ranges");
+}
+#undef RAC_OPTIM_DISPATCH
 
 }  // extern "C"
 

@@ -27,7 +27,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import AbsmaxJob, AdamFragJob, AdamRange, ConvArgs, FragJob, GradSrc, WgradArgs, call, ptr, stream_ptr
+from ._lib import (AbsmaxJob, AdamFragJob, AdamRange, ConvArgs, FragJob, GradSrc, OptimRange, WgradArgs, call, ptr,
+                   stream_ptr)
 
 FWD, DGRAD, WGRAD = 0, 1, 2
 ACT_NONE, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2
@@ -501,7 +502,8 @@ def _wp_state(device):
     if st is None:
         st = _WP_DEV[device] = {"slots": torch.zeros(_WP_NSLOTS, device=device, dtype=torch.int32),
                                 "exact": torch.zeros(_WP_NSLOTS, device=device, dtype=torch.int32),
-                                "free": list(range(_WP_NSLOTS - 1, -1, -1)), "tables": {}, "adam_plan": None}
+                                "free": list(range(_WP_NSLOTS - 1, -1, -1)), "tables": {}, "adam_plan": None,
+                                "optim_plan": None}
     return st
 
 
@@ -568,6 +570,35 @@ def param_wait(t: torch.Tensor = None) -> None:
         gate.wait_params()
 
 
+def _wp_tables(st, items, device):
+    """Job tables (device memory, cached per set of weights) of rac_absmax_multi / rac_weight_frag_split_multi over
+    `items` = [(entry, weight)]: (absmax jobs, n, blocks, fragment jobs, n, blocks, the entries' slot indices)."""
+    lib = _lib.load()
+    sig = tuple((w.data_ptr(), ent.idx, tuple(sorted((t, q.data_ptr()) for t, q in ent.parts.items())))
+                for ent, w in items)
+    tables = st["tables"].get(sig)
+    if tables is None:  # job tables (device memory) for this set of weights
+        if len(st["tables"]) > 8:
+            st["tables"].clear()
+        ajobs = (AbsmaxJob * len(items))()
+        nfrag = sum(len(ent.parts) for ent, _ in items)
+        fjobs = (FragJob * nfrag)()
+        ab = fb = j = 0
+        for i, (ent, w) in enumerate(items):
+            wm = weight_mem(w.detach())
+            co, ci, k, _ = w.shape
+            ajobs[i] = AbsmaxJob(x=ptr(wm), n=wm.numel(), amax=ptr(ent.slot), block_begin=ab)
+            ab += lib.rac_absmax_blocks(wm.numel())
+            for transposed, parts in sorted(ent.parts.items()):
+                fjobs[j] = FragJob(w=ptr(wm), w_amax=ptr(ent.slot), parts=ptr(parts), part_stride=wm.numel(), Cout=co,
+                                   Cin=ci, ksize=k, transposed=1 if transposed else 0, block_begin=fb)
+                fb += lib.rac_weight_frag_blocks(co, ci, k)
+                j += 1
+        idx = torch.tensor([ent.idx for ent, _ in items], device=device, dtype=torch.long)
+        tables = st["tables"][sig] = (_wp_upload(ajobs, device), len(items), ab, _wp_upload(fjobs, device), nfrag, fb, idx)
+    return tables
+
+
 def _wp_refresh(device):
     """Bring every registered weight of `device` whose parameter changed up to date."""
     st = _wp_state(device)
@@ -595,7 +626,6 @@ def _wp_refresh(device):
     if not stale:
         return
     sp = stream_ptr()
-    lib = _lib.load()
     if len(stale) <= 2:  # a new registration: the single-tensor calls
         for ent, w in stale:
             ent.slot.zero_()
@@ -608,29 +638,7 @@ def _wp_refresh(device):
             st["exact"][ent.idx:ent.idx + 1].copy_(ent.slot)
             ent.tag, ent.exact_ok = _wp_tag(w), True
         return
-    sig = tuple((w.data_ptr(), ent.idx, tuple(sorted((t, q.data_ptr()) for t, q in ent.parts.items())))
-                for ent, w in stale)
-    tables = st["tables"].get(sig)
-    if tables is None:  # job tables (device memory) for this set of weights
-        if len(st["tables"]) > 8:
-            st["tables"].clear()
-        ajobs = (AbsmaxJob * len(stale))()
-        nfrag = sum(len(ent.parts) for ent, _ in stale)
-        fjobs = (FragJob * nfrag)()
-        ab = fb = j = 0
-        for i, (ent, w) in enumerate(stale):
-            wm = weight_mem(w.detach())
-            co, ci, k, _ = w.shape
-            ajobs[i] = AbsmaxJob(x=ptr(wm), n=wm.numel(), amax=ptr(ent.slot), block_begin=ab)
-            ab += lib.rac_absmax_blocks(wm.numel())
-            for transposed, parts in sorted(ent.parts.items()):
-                fjobs[j] = FragJob(w=ptr(wm), w_amax=ptr(ent.slot), parts=ptr(parts), part_stride=wm.numel(), Cout=co,
-                                   Cin=ci, ksize=k, transposed=1 if transposed else 0, block_begin=fb)
-                fb += lib.rac_weight_frag_blocks(co, ci, k)
-                j += 1
-        idx = torch.tensor([ent.idx for ent, _ in stale], device=device, dtype=torch.long)
-        tables = st["tables"][sig] = (_wp_upload(ajobs, device), len(stale), ab, _wp_upload(fjobs, device), nfrag, fb, idx)
-    ta, na, ab, tf, nf, fb, idx = tables
+    ta, na, ab, tf, nf, fb, idx = _wp_tables(st, stale, device)
     st["slots"].index_fill_(0, idx, 0)  # the stale slots are recomputed (the others may hold bounds of a fused step)
     call("rac_absmax_multi", ptr(ta), na, ab, sp)
     call("rac_weight_frag_split_multi", ptr(tf), nf, fb, sp)
@@ -671,6 +679,30 @@ def adam_step_bound(beta1: float, beta2: float):
     return _ADAM_BOUNDS[key]
 
 
+def _wp_covered(flat):
+    """[(first flat element, entry, weight)] of the registered split-precision weights that live in the flat parameter buffer
+    (16-byte aligned, [Cout][k][k][Cin] memory; not the zero-padded copies), in flat order -- None as soon as one of them
+    has parts or a maximum that are not current (first steps, new registrations): a fused optimiser step must wait."""
+    dev = flat.device
+    base, nbytes = flat.data_ptr(), flat.numel() * 4
+    covered = []
+    for ent in _WP_ENTRIES.values():
+        if ent.device != dev:
+            continue
+        w = ent.ref()
+        if w is None or getattr(w, "_rac_pad_source", None) is not None:
+            continue
+        off = w.data_ptr() - base
+        co, ci, k, _ = w.shape
+        if not (0 <= off < nbytes and off % 16 == 0 and w.stride() == (k * k * ci, 1, k * ci, ci)):
+            continue
+        if ent.tag != _wp_tag(w) or not ent.exact_ok:
+            return None
+        covered.append((off // 4, ent, w))
+    covered.sort(key=lambda c: c[0])
+    return covered
+
+
 def fused_adam_step(flat, grad, m, v, lr, beta1, beta2, eps, step, late=None):
     """One optimiser step over the flat buffers with the registered split-precision weights' parts refreshed in the
     same pass.  False (nothing launched) when that is not possible yet -- a weight whose parts or maximum are not
@@ -691,24 +723,10 @@ def fused_adam_step(flat, grad, m, v, lr, beta1, beta2, eps, step, late=None):
         return False
     dev = flat.device
     st = _wp_state(dev)
-    base, nbytes = flat.data_ptr(), flat.numel() * 4
-    covered = []
-    for ent in _WP_ENTRIES.values():
-        if ent.device != dev:
-            continue
-        w = ent.ref()
-        if w is None or getattr(w, "_rac_pad_source", None) is not None:
-            continue
-        off = w.data_ptr() - base
-        co, ci, k, _ = w.shape
-        if not (0 <= off < nbytes and off % 16 == 0 and w.stride() == (k * k * ci, 1, k * ci, ci)):
-            continue
-        if ent.tag != _wp_tag(w) or not ent.exact_ok:
-            return False
-        covered.append((off // 4, ent, w))
+    base = flat.data_ptr()
+    covered = _wp_covered(flat)
     if not covered:
         return False
-    covered.sort(key=lambda c: c[0])
     # late[1]: one set of data pointers, or a LIST of sets = groups in the order the next forward pass needs them (each
     # group its own launch and event on the side stream, which runs them in that order)
     late_sets = [] if late is None else (list(late[1]) if isinstance(late[1], (list, tuple)) else [late[1]])
@@ -815,6 +833,66 @@ def fused_adam_step(flat, grad, m, v, lr, beta1, beta2, eps, step, late=None):
     for _, ent, w in covered:  # their parts and maxima already describe the new values
         ent.tag = _wp_tag(w)
     return done if done else True
+
+
+# RMSprop / SGD (optim.FusedRMSprop, optim.FusedSGD): ONE launch updates the whole flat buffer from a range table in which
+# every registered split-precision weight is a range of its own that carries its amax slot (rac_optim_ranges), so the
+# exact new maxima come out of the update; rac_weight_frag_split_multi then writes the parts scaled by them -- the pass
+# for the maxima (rac_absmax_multi) is gone, the fragment pass stays.  No single pass in the manner of fused_adam_step:
+# it needs a bound of the step BEFORE the new maximum is known, RMSprop's only rigorous one is lr / sqrt(1 - alpha) (0.1 at
+# torch's defaults: the size of the weights) and SGD has none -- a scale from such a bound would drop operand bits.
+def fused_optim_step(rule, flat, grad, state0, state1, lr, momentum=0.0, gain=1.0, alpha=0.0, eps=0.0, flags=0):
+    """One RMSprop / SGD step (include/rac_hip.h: rac_optim_step's rules and arguments; state tensors a rule does not have
+    are None) over the flat buffers that leaves the registered split-precision weights' maxima and parts current.  False
+    (nothing launched) when that is not possible yet -- a weight whose parts or maximum are not current (first steps, new
+    registrations), no registered weight inside `flat`, a layout the table does not describe: the caller then takes
+    rac_optim_step over the flat buffer and the parts are refreshed lazily (_wp_refresh)."""
+    global PARAM_EPOCH
+    dev = flat.device
+    st = _wp_state(dev)
+    base = flat.data_ptr()
+    covered = _wp_covered(flat)
+    if not covered:
+        return False
+    sig = (base, grad.data_ptr(), ptr(state0), ptr(state1),
+           tuple((off, ent.idx, tuple(sorted((t, q.data_ptr()) for t, q in ent.parts.items()))) for off, ent, _ in covered))
+    plan = st["optim_plan"]
+    if plan is not None and plan["sig"] == sig and plan.get("unsupported"):
+        return False
+    if plan is None or plan["sig"] != sig:
+        ranges, pos = [], 0
+        for off, ent, w in covered:
+            n = w.numel()
+            if off % 4 or n % 4 or off < pos or off + n > flat.numel() or flat.numel() % 4:
+                # registered views that overlap (the merged mu | logvar head next to its own two parameters) or are not
+                # 16-byte aligned: not this table's layout -- the plain step, parts refreshed lazily (as fused_adam_step)
+                st["optim_plan"] = {"sig": sig, "unsupported": True}
+                return False
+            if off > pos:
+                ranges.append((pos // 4, (off - pos) // 4, None))
+            ranges.append((off // 4, n // 4, ptr(ent.slot)))
+            pos = off + n
+        if pos < flat.numel():
+            ranges.append((pos // 4, (flat.numel() - pos) // 4, None))
+        rjobs = (OptimRange * len(ranges))()
+        rblocks = 0
+        for i, (b4, n4, slot) in enumerate(ranges):
+            rjobs[i] = OptimRange(begin4=b4, n4=n4, block_begin=rblocks, amax=slot)
+            rblocks += _cdiv(n4, 1024)
+        _, _, _, tf, nf, fb, idx = _wp_tables(st, [(ent, w) for _, ent, w in covered], dev)
+        plan = st["optim_plan"] = {"sig": sig, "ranges": _wp_upload(rjobs, dev), "n_ranges": len(ranges), "rblocks": rblocks,
+                                   "frag": tf, "n_frag": nf, "frag_blocks": fb, "idx": idx}
+    sp = stream_ptr()
+    idx = plan["idx"]
+    st["slots"].index_fill_(0, idx, 0)  # the update folds the new maxima into zeroed slots
+    call("rac_optim_ranges", ptr(flat), ptr(grad), ptr(state0), ptr(state1), ptr(plan["ranges"]), plan["n_ranges"],
+         plan["rblocks"], int(rule), int(flags), float(lr), float(momentum), float(gain), float(alpha), float(eps), sp)
+    call("rac_weight_frag_split_multi", ptr(plan["frag"]), plan["n_frag"], plan["frag_blocks"], sp)
+    st["exact"].index_copy_(0, idx, st["slots"].index_select(0, idx))
+    PARAM_EPOCH += 1
+    for _, ent, w in covered:  # their parts and maxima already describe the new values
+        ent.tag = _wp_tag(w)
+    return True
 
 
 def weight_parts(weight: torch.Tensor, transposed: bool = False):

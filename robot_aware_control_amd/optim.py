@@ -1,7 +1,10 @@
 """Fused Adam over the model's flat parameter buffer (one HIP launch per step).
 
 State-dict compatible with `torch.optim.Adam` (reference trainer.py:109-122,829-837): per-parameter
-`step`, `exp_avg`, `exp_avg_sq` entries are views of two flat moment buffers."""
+`step`, `exp_avg`, `exp_avg_sq` entries are views of two flat moment buffers.
+
+`FusedRMSprop` / `FusedSGD` are the flag's other two values (`--optimizer rmsprop | sgd`), likewise over the flat buffers
+and interchangeable with `torch.optim.RMSprop` / `torch.optim.SGD` state dicts; `make_optimizer` maps the flag."""
 from __future__ import annotations
 
 import os
@@ -317,3 +320,181 @@ class ShardedAdam(FusedAdam):
             pos += n
         self._steps = steps
         self.state.clear()
+
+
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What FusedRMSprop and FusedSGD share: one HIP launch per step over the model's flat buffers (ops.fused_optim_step:
+    the update that also leaves the split-precision conv weights' maxima, then their parts; rac_optim_step over the whole
+    buffer while the parts are not current yet), flat state buffers allocated on first use, and a state dict whose
+    per-parameter entries are views of them under torch's names.
+
+    Not a FusedAdam: the trainer turns the late-update overlap on by isinstance, and these have no late groups -- every
+    weight is updated on the caller's stream, so the waits the trainer and ops.PARAM_GATE users call have nothing to do."""
+    _RULE = None
+    _STATE = ()  # torch's names of (state0, state1) of rac_optim_step, for the buffers the hyper-parameters call for
+
+    def __init__(self, model, defaults):
+        super().__init__(list(model.parameters()), defaults)
+        self._check(self.param_groups[0])
+        self._model = model
+        self._steps = 0
+        self._bufs = {}
+
+    def wait_params(self, upto: int = None):
+        pass
+
+    def wait_for(self, t: torch.Tensor):
+        pass
+
+    def ready(self, t: torch.Tensor) -> bool:
+        return True
+
+    @staticmethod
+    def _check(g):
+        for key in ("weight_decay", "maximize", "centered", "differentiable", "capturable"):
+            if g.get(key):
+                raise ValueError("%s=%r is not built on the HIP path" % (key, g[key]))
+        if g["momentum"] < 0:
+            raise ValueError("Invalid momentum value: %r" % (g["momentum"],))
+
+    def _names(self, g):
+        """Names of the state buffers these hyper-parameters use, None where rac_optim_step takes NULL."""
+        raise NotImplementedError
+
+    def _buffer(self, name):
+        flat, _ = self._model.flat_parameters()
+        buf = self._bufs.get(name)
+        if buf is None or buf.numel() != flat.numel() or buf.device != flat.device:
+            buf = self._bufs[name] = torch.zeros_like(flat)
+        return buf
+
+    def _hyper(self, g):
+        """(momentum, gain, alpha, eps, flags) of rac_optim_step for the step about to be taken."""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        flat, grad = self._model.flat_parameters()
+        if not flat.is_cuda:
+            raise _lib.RacError("%s runs on the GPU only" % type(self).__name__)
+        g = self.param_groups[0]
+        self._check(g)
+        s0, s1 = (None if name is None else self._buffer(name) for name in self._names(g))
+        momentum, gain, alpha, eps, flags = self._hyper(g)
+        self._steps += 1
+        if ops._STALE:  # a lazy zero_grad whose step never reached finish_grads(): no stale gradient is ever applied
+            ops.finish_grads()
+        if ops.fused_optim_step(self._RULE, flat, grad, s0, s1, g["lr"], momentum, gain, alpha, eps, flags):
+            return
+        ops.PARAM_EPOCH += 1  # invalidates caches derived from the parameters (padded weight copies, operand parts)
+        _lib.call("rac_optim_step", flat.data_ptr(), grad.data_ptr(), _lib.ptr(s0), _lib.ptr(s1), flat.numel(), self._RULE,
+                  int(flags), float(g["lr"]), float(momentum), float(gain), float(alpha), float(eps), _lib.stream_ptr())
+
+    def _views(self, names):
+        bufs = [self._buffer(name) for name in names]
+        for p in self.param_groups[0]["params"]:
+            off = p._rac_off  # the parameter's place in the model's flat buffer (SVGConvModel._flatten)
+            yield p, [torch.as_strided(b, p.shape, p.stride(), off) for b in bufs]
+
+
+class FusedRMSprop(_FlatOptimizer):
+    """torch.optim.RMSprop (centered=False, weight_decay=0; reference trainer.py:111-113) over the model's flat buffers.
+    State-dict compatible with it: per-parameter `step` (a float tensor), `square_avg` and, with momentum > 0,
+    `momentum_buffer` are views of flat buffers."""
+    _RULE = _lib.OPTIM_RMSPROP
+
+    def __init__(self, model, lr=1e-2, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0, centered=False, maximize=False):
+        super().__init__(model, dict(lr=lr, momentum=momentum, alpha=alpha, eps=eps, centered=centered,
+                                     weight_decay=weight_decay, capturable=False, foreach=None, maximize=maximize,
+                                     differentiable=False))
+
+    def _names(self, g):
+        return ("square_avg", "momentum_buffer" if g["momentum"] > 0 else None)
+
+    def _hyper(self, g):
+        return g["momentum"], 1 - g["alpha"], g["alpha"], g["eps"], 0
+
+    def state_dict(self):
+        if self._steps:
+            names = [n for n in self._names(self.param_groups[0]) if n]
+            for p, views in self._views(names):
+                self.state[p] = dict(zip(names, views), step=torch.tensor(float(self._steps)))
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._check(self.param_groups[0])
+        names = [n for n in self._names(self.param_groups[0]) if n]
+        steps = 0
+        for p, views in self._views(names):
+            st = self.state.get(p)
+            if st:
+                for name, view in zip(names, views):
+                    view.copy_(st[name])
+                steps = max(steps, int(st["step"]))
+        self._steps = steps
+        self.state.clear()
+
+
+class FusedSGD(_FlatOptimizer):
+    """torch.optim.SGD (weight_decay=0; reference trainer.py:114-116) over the model's flat buffers.  State-dict compatible
+    with it: with momentum the per-parameter `momentum_buffer` is a view of one flat buffer, without it the state is
+    empty.  torch's SGD keeps no step count: all that survives a state dict is whether the buffers exist (a
+    `momentum_buffer` of None, or no state, means the next step is the first: buf = g)."""
+    _RULE = _lib.OPTIM_SGD
+
+    def __init__(self, model, lr=1e-3, momentum=0, dampening=0, nesterov=False, weight_decay=0, maximize=False):
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(model, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                     nesterov=nesterov, maximize=maximize, foreach=None, differentiable=False, fused=None))
+
+    def _names(self, g):
+        return ("momentum_buffer" if g["momentum"] != 0 else None, None)
+
+    def _hyper(self, g):
+        flags = (_lib.OPTIM_NESTEROV if g["nesterov"] else 0) | (_lib.OPTIM_FIRST_STEP if self._steps == 0 else 0)
+        return g["momentum"], 1 - g["dampening"], 0.0, 0.0, flags
+
+    def state_dict(self):
+        if self._steps and self.param_groups[0]["momentum"] != 0:
+            for p, (view,) in self._views(["momentum_buffer"]):
+                self.state[p] = {"momentum_buffer": view}
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._check(self.param_groups[0])
+        have = []
+        if self.param_groups[0]["momentum"] != 0:
+            for p, (view,) in self._views(["momentum_buffer"]):
+                buf = (self.state.get(p) or {}).get("momentum_buffer")
+                have.append(buf is not None)
+                if buf is not None:
+                    view.copy_(buf)
+        if any(have) and not all(have):
+            raise ValueError("FusedSGD: momentum_buffer present for some parameters only (one flat buffer, one first step)")
+        self._steps = 1 if any(have) else 0
+        self.state.clear()
+
+
+def make_optimizer(cf, model, sharded: bool):
+    """The optimiser `--optimizer` names (reference trainer.py:109-122).  "adam" takes --lr and --beta1; "rmsprop" and
+    "sgd" run with torch's defaults, --lr NOT applied: the reference builds them as bare classes and calls
+    `optimizer(params)`.  `sharded`: --ddp_shard_optimizer True in a process group (Adam only)."""
+    if cf.optimizer not in ("adam", "rmsprop", "sgd"):
+        raise ValueError("Unknown optimizer on the HIP path: %s" % cf.optimizer)
+    if cf.optimizer != "adam":
+        if sharded:
+            raise ValueError("--ddp_shard_optimizer True is built for --optimizer adam only (got --optimizer %s)"
+                             % cf.optimizer)
+        return FusedRMSprop(model) if cf.optimizer == "rmsprop" else FusedSGD(model)
+    if sharded and not ShardedAdam.supports(model, dist.get_world_size()):
+        # equal 16-byte-aligned slices need the flat buffers (padded to 1024 elements) to divide by 4 * world
+        import warnings
+        warnings.warn("--ddp_shard_optimizer needs a world size that divides 256 (got %d): "
+                      "using all-reduce + the full Adam step instead" % dist.get_world_size())
+        sharded = False
+    if sharded:
+        return ShardedAdam(model, lr=cf.lr, betas=(cf.beta1, 0.999), bucket_mb=getattr(cf, "ddp_bucket_mb", 64))
+    return FusedAdam(model, lr=cf.lr, betas=(cf.beta1, 0.999))

@@ -22,7 +22,7 @@ import torch.distributed as dist
 
 from . import ops, parallel_env
 from .model import SVGConvModel
-from .optim import FusedAdam, ShardedAdam
+from .optim import FusedAdam, ShardedAdam, make_optimizer
 
 # teacher-forced windows run the encoder / decoder once over all time steps (RAC_SEQUENCE_PATH=0: step by step)
 SEQUENCE_PATH = os.environ.get("RAC_SEQUENCE_PATH", "1") == "1"
@@ -163,20 +163,8 @@ class PredictionTrainer(object):
         self.model = SVGConvModel(cf).to(self._device)
         if _dist_on():  # identical initial weights on every rank
             dist.broadcast(self.model.flat_parameters()[0], src=0)
-        if cf.optimizer != "adam":
-            raise ValueError("Unknown optimizer on the HIP path: %s" % cf.optimizer)
-        shard = getattr(cf, "ddp_shard_optimizer", False) and _dist_on()
-        if shard and not ShardedAdam.supports(self.model, dist.get_world_size()):
-            # equal 16-byte-aligned slices need the flat buffers (padded to 1024 elements) to divide by 4 * world
-            import warnings
-            warnings.warn("--ddp_shard_optimizer needs a world size that divides 256 (got %d): "
-                          "using all-reduce + the full Adam step instead" % dist.get_world_size())
-            shard = False
-        if shard:
-            self.optimizer = ShardedAdam(self.model, lr=cf.lr, betas=(cf.beta1, 0.999),
-                                         bucket_mb=getattr(cf, "ddp_bucket_mb", 64))
-        else:
-            self.optimizer = FusedAdam(self.model, lr=cf.lr, betas=(cf.beta1, 0.999))
+        # --optimizer adam | rmsprop | sgd (trainer.py:109-122); anything else is the reference's ValueError
+        self.optimizer = make_optimizer(cf, self.model, bool(getattr(cf, "ddp_shard_optimizer", False) and _dist_on()))
 
     def _schedule_prob(self):
         """Probability of feeding ground truth (trainer.py:132-140)."""
