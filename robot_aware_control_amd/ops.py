@@ -333,14 +333,8 @@ def bias_grad_acc(dy, bias):
 
 
 # bias gradients are summed in two stages -- per row block, then the blocks in a fixed order -- so that a train step is
-# bit-reproducible (one fp32 atomic per workgroup and column was the step's last order-dependent fp32 sum);
-# RAC_COLSUM_ATOMIC=1: the atomics
-COLSUM_ATOMIC = os.environ.get("RAC_COLSUM_ATOMIC", "0") == "1"
-
-
+# bit-reproducible (one fp32 atomic per workgroup and column was the step's last order-dependent fp32 sum)
 def _colsum_parts(device, M: int, Cc: int):
-    if COLSUM_ATOMIC:
-        return None
     return torch.empty(int(_lib.load().rac_colsum_blocks(M, Cc)) * Cc, device=device, dtype=torch.float32)
 
 
@@ -531,24 +525,8 @@ def _wp_upload(jobs, device):
 
 _ADAM_SIDE = {"stream": None}  # fused_adam_step(late=...): the late weights' update runs here
 ADAM_LATE_WGS = int(os.environ.get("RAC_ADAM_LATE_WGS", "512"))  # ... on this many workgroups (2 per CU)
-ADAM_LOW_PRIORITY = os.environ.get("RAC_ADAM_LOW_PRIORITY", "0") == "1"  # (experiments: a below-default-priority HIP stream)
 ADAM_WGS = int(os.environ.get("RAC_ADAM_WGS", "0"))  # (experiments: the one-stream pass on a bounded grid too; 0 = one workgroup per block)
 
-
-def low_priority_stream(dev):
-    """A HIP stream BELOW the default priority (torch offers only default and higher): its workgroups take the slots the
-    default-priority streams leave.  Falls back to a plain stream if the runtime refuses."""
-    try:
-        hip = C.CDLL("libamdhip64.so")
-        lo, hi = C.c_int(0), C.c_int(0)
-        if hip.hipDeviceGetStreamPriorityRange(C.byref(lo), C.byref(hi)) == 0 and lo.value > 0:
-            with torch.cuda.device(dev):
-                h = C.c_void_p()
-                if hip.hipStreamCreateWithPriority(C.byref(h), C.c_uint(1), C.c_int(lo.value)) == 0 and h.value:  # 1: non-blocking
-                    return torch.cuda.ExternalStream(h.value, device=dev)
-    except OSError:
-        pass
-    return torch.cuda.Stream(device=dev)
 
 # optim.ShardedAdam while the all-gather of the updated parameters is in flight (or optim.FusedAdam while its late weights'
 # update runs on the side stream): `ready(param)` says whether a parameter's
@@ -814,7 +792,7 @@ def fused_adam_step(flat, grad, m, v, lr, beta1, beta2, eps, step, late=None):
     if n_late:
         main = torch.cuda.current_stream()
         if _ADAM_SIDE["stream"] is None or _ADAM_SIDE["stream"].device != dev:
-            _ADAM_SIDE["stream"] = low_priority_stream(dev) if ADAM_LOW_PRIORITY else torch.cuda.Stream(device=dev)
+            _ADAM_SIDE["stream"] = torch.cuda.Stream(device=dev)
         side = _ADAM_SIDE["stream"]
         ready = torch.cuda.Event()
         ready.record(main)  # every gradient, the scale bounds and whatever read the old weights precede the side launch
@@ -1168,29 +1146,13 @@ WGRAD_ALLKY = os.environ.get("RAC_WGRAD_ALLKY", "1") == "1"
 WGRAD_STREAM = os.environ.get("RAC_WGRAD_STREAM", "1") == "1"
 WGRAD_CHAIN_FLUSH = os.environ.get("RAC_WGRAD_CHAIN_FLUSH", "1") == "1"  # per ConvLSTM chain (0: once, behind the core)
 _SIDE = {"stream": None, "done": None, "keep": [], "on_ready": None}
-WGRAD_LOW_PRIORITY = os.environ.get("RAC_WGRAD_LOW_PRIORITY", "0") == "1"  # (experiment: the side stream below default priority)
-WGRAD_CU_MASK = os.environ.get("RAC_WGRAD_CU_MASK", "")  # (experiment: hex CU mask of the side stream, e.g. 3/4 of every XCD)
 
 
 def _side_stream(dev):
     """The stream the weight gradients run on, beside the data-gradient chain."""
     st = _SIDE["stream"]
     if st is None or st.device != torch.device(dev):
-        st = None
-        if WGRAD_CU_MASK:
-            try:
-                hip = C.CDLL("libamdhip64.so")
-                words = [int(WGRAD_CU_MASK[max(0, i - 8):i], 16) for i in range(len(WGRAD_CU_MASK), 0, -8)]
-                arr = (C.c_uint32 * len(words))(*words)
-                with torch.cuda.device(dev):
-                    h = C.c_void_p()
-                    if hip.hipExtStreamCreateWithCUMask(C.byref(h), C.c_uint32(len(words)), arr) == 0 and h.value:
-                        st = torch.cuda.ExternalStream(h.value, device=dev)
-            except (OSError, AttributeError):
-                st = None
-        if st is None:
-            st = low_priority_stream(dev) if WGRAD_LOW_PRIORITY else torch.cuda.Stream(device=dev)
-        _SIDE["stream"] = st
+        st = _SIDE["stream"] = torch.cuda.Stream(device=dev)
     return st
 
 
@@ -1714,12 +1676,6 @@ class ConvTHead(torch.autograd.Function):
         return dx, None, None, None
 
 
-# One time step's small vgg layers with BatchNorm in ONE launch each way (rac_bn_small_fwd / _bwd: a workgroup owns a slice of
-# channels and all rows -- no atomics, no second launch).  Built, tested (the same numbers to 2e-6) and measured SLOWER: with
-# every frame fed back 38.0 ms per step against 33.2 (4 MB layers; 34.6 with 2 MB, 42-53 with 8-16 MB), the deployed model's
-# stepped window 28.0 against 25.4 -- 32-64 workgroups walking 1 024+ rows of 8 slabs each are bound by what ONE workgroup
-# keeps in flight, and lose more than the two launches and their atomics cost.  Off; RAC_BN_SMALL=1 turns it on.
-BN_SMALL = os.environ.get("RAC_BN_SMALL", "0") == "1"
 BN_FUSED_APPLY = os.environ.get("RAC_BN_FUSED_APPLY", "1") == "1"  # BatchNorm finalize + affine + LeakyReLU in one launch
 
 
@@ -1775,23 +1731,6 @@ class VggLayer(torch.autograd.Function):
         c0 = x0.shape[3]
         ctx.split = (SPLIT_GEMM and Cout >= SPLIT_MIN_COUT_TRAIN
                      and split_supported(x0.shape[1], x0.shape[2], 3, weight.shape[1], Cout, c0 if x1 is not None else 0))
-        Mx = x0.shape[0] * x0.shape[1] * x0.shape[2]
-        ctx.small = bool(ctx.split and G == 1 and BN_SMALL and _lib.load().rac_bn_small_ok(Mx, Cout))
-        if ctx.small:
-            # one time step's small layer (a window that feeds its frames back): split-K combine + statistics + affine +
-            # LeakyReLU in ONE launch whose workgroups each own a slice of channels (rac_bn_small_fwd)
-            slabs, n_slabs, stride = conv_forward_split(x0, x1, weight, want_slabs=True)
-            raw = slabs[0] if n_slabs == 1 else torch.empty(tuple(slabs.shape[1:]), device=dev, dtype=torch.float32)
-            aff = torch.empty((4, 1, Cout), device=dev, dtype=torch.float32)
-            y = torch.empty_like(raw)
-            slot = amax_slot(dev)
-            call("rac_bn_small_fwd", ptr(slabs), n_slabs, stride, ptr(raw), ptr(y), ptr(gamma), ptr(beta), ptr(rmean),
-                 ptr(rvar), BN_MOMENTUM, BN_EPS, n_updates, ptr(aff[0]), ptr(aff[1]), ptr(aff[2]), ptr(aff[3]), Mx, Cout,
-                 ACT_LEAKY, ptr(slot), stream_ptr())
-            tag_amax(y, slot)
-            ctx.save_for_backward(x0, x1, wfull, gamma, beta, raw, aff)
-            ctx.amax = (amax_tag(x0), amax_tag(x1))
-            return y
         if ctx.split:
             raw = conv_forward_split(x0, x1, weight, None, stats=stats, groups=G)
         else:
@@ -1813,18 +1752,13 @@ class VggLayer(torch.autograd.Function):
         G = ctx.groups
         draw = torch.empty_like(raw)
         want_affine = gamma.requires_grad
-        if ctx.small:  # (reduce + apply in one launch: rac_bn_small_bwd)
-            call("rac_bn_small_bwd", ptr(dy), ptr(raw), ptr(aff[0]), ptr(aff[1]), ptr(aff[2]), ptr(aff[3]), ptr(draw),
-                 ptr(grad_buffer(gamma)) if want_affine else None, ptr(grad_buffer(beta)) if want_affine else None, M, Cout,
-                 ptr(tag_amax(draw, amax_slot(dy.device))._rac_amax), stream_ptr())
-        else:
-            sums = zeros64((G, 2, Cout), dy.device)
-            call("rac_bn_bwd_reduce", ptr(dy), ptr(raw), ptr(aff[0]), ptr(aff[1]), ptr(aff[2]), ptr(aff[3]), ptr(sums), M,
-                 Cout, G, stream_ptr())
-            call("rac_bn_bwd_apply", ptr(dy), ptr(raw), ptr(aff[0]), ptr(aff[1]), ptr(aff[2]), ptr(aff[3]), ptr(sums),
-                 ptr(draw), ptr(grad_buffer(gamma)) if want_affine else None,
-                 ptr(grad_buffer(beta)) if want_affine else None, M, Cout, G,
-                 ptr(tag_amax(draw, amax_slot(dy.device))._rac_amax), stream_ptr())
+        sums = zeros64((G, 2, Cout), dy.device)
+        call("rac_bn_bwd_reduce", ptr(dy), ptr(raw), ptr(aff[0]), ptr(aff[1]), ptr(aff[2]), ptr(aff[3]), ptr(sums), M,
+             Cout, G, stream_ptr())
+        call("rac_bn_bwd_apply", ptr(dy), ptr(raw), ptr(aff[0]), ptr(aff[1]), ptr(aff[2]), ptr(aff[3]), ptr(sums),
+             ptr(draw), ptr(grad_buffer(gamma)) if want_affine else None,
+             ptr(grad_buffer(beta)) if want_affine else None, M, Cout, G,
+             ptr(tag_amax(draw, amax_slot(dy.device))._rac_amax), stream_ptr())
         C0 = x0.shape[3]
         C1 = x1.shape[3] if x1 is not None else 0
         dx0 = dx1 = None

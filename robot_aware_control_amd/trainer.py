@@ -26,7 +26,6 @@ from .optim import FusedAdam, ShardedAdam, make_optimizer
 
 # teacher-forced windows run the encoder / decoder once over all time steps (RAC_SEQUENCE_PATH=0: step by step)
 SEQUENCE_PATH = os.environ.get("RAC_SEQUENCE_PATH", "1") == "1"
-STEP_HIGH_PRIORITY = os.environ.get("RAC_STEP_HIGH_PRIORITY", "0") == "1"
 
 
 def _dist_on() -> bool:
@@ -255,20 +254,6 @@ class PredictionTrainer(object):
     def _train_step(self, data, use_truth=None):
         """Forward and backward pass + optimiser step (trainer.py:326-465).  Returns the loss dict.
         `use_truth[i]` overrides the scheduled-sampling coin at time index i (parity tests)."""
-        if STEP_HIGH_PRIORITY:
-            # (experiment) the whole step on a HIGH-priority stream: when the side stream's weight-gradient workgroups retire,
-            # the step's own small kernels get the freed slots first
-            if getattr(self, "_hp_stream", None) is None:
-                self._hp_stream = torch.cuda.Stream(device=self._device, priority=-1)
-            cur = torch.cuda.current_stream()
-            self._hp_stream.wait_stream(cur)
-            with torch.cuda.stream(self._hp_stream):
-                out = self._train_step_body(data, use_truth)
-            cur.wait_stream(self._hp_stream)
-            return out
-        return self._train_step_body(data, use_truth)
-
-    def _train_step_body(self, data, use_truth=None):
         cf = self._config
         dev = self._device
         f32 = torch.float32
@@ -401,10 +386,8 @@ class PredictionTrainer(object):
         # that step's backward pass; the hand-scheduled core launches its chains' gradients itself
         stepped = not (sequence_taken and self.model.used_recurrent_core)
         try:
-            fl = os.environ.get("RAC_SCHED_FLUSH")  # (experiments: "4,5" = flush points; default: the window's step count)
-            points = tuple(int(v) for v in fl.split(",")) if fl else n_steps
             with ops.deferred_wgrad(on_ready=reducer.ready if reducer is not None else None,
-                                    flush_after=points if stepped else None,
+                                    flush_after=n_steps if stepped else None,
                                     vgg_steps=not sequence_taken):
                 torch.autograd.backward(roots, seeds)
                 self._mark("backward")

@@ -342,7 +342,7 @@ def test_recurrent_core_chain_streams_same_bits(dev, monkeypatch):
         for name, a, b in zip(("outputs", "input gradients", "weight gradients"), got[:3], ref[:3]):
             for i, (x, y) in enumerate(zip(a, b)):
                 assert torch.equal(x, y), (rep, name, i, float((x - y).abs().max()))
-        for x, y in zip(got[3], ref[3]):  # (bias gradients: column sums with fp32 atomics)
+        for x, y in zip(got[3], ref[3]):  # (bias gradients: two-stage column sums in a fixed order, no atomics)
             assert float((x - y).norm() / (y.norm() + 1e-30)) < 1e-5
 
 
