@@ -680,9 +680,16 @@ __global__ __launch_bounds__(256) void slab_reduce_stats_rows_kernel(const f32x4
   s1[tid] = a1;
   s2[tid] = a2;
   __syncthreads();
+  // C < 64 (pass heights of 32 .. 256 rows; rpi >= 16 always, a slice has at most 16 quads): the row lanes fold pairwise down
+  // to 16 before one thread adds them in a chain -- a chain of 256 fp32 partials lost 2.2e-6 of a zero-mean group's sum at
+  // C = 4 (tests/test_gpu_reduce.py).  C >= 64 has 16 row lanes: no fold, the same additions in the same order as before.
+  for (int h = rpi >> 1; h >= 16; h >>= 1) {
+    if (rl < h) s1[tid] += s1[tid + h * C4s], s2[tid] += s2[tid + h * C4s];
+    __syncthreads();
+  }
   if (tid < C4s) {
     f32x4 t1 = s1[tid], t2 = s2[tid];
-    for (int k = 1; k < rpi; ++k) t1 += s1[k * C4s + tid], t2 += s2[k * C4s + tid];
+    for (int k = 1; k < 16; ++k) t1 += s1[k * C4s + tid], t2 += s2[k * C4s + tid];
     double* sg = stats + (long)g * 8 * C4 + 4 * c4;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
