@@ -451,6 +451,27 @@ int rac_composite_fwd(const float* x4, const float* prev, float* out, int32_t B,
 int rac_composite_bwd(const float* dout, const float* x4, const float* prev, float* dx4, float* dprev, int32_t B,
                       int32_t HW, void* stream);
 
+/* The deterministic baselines (dynamics.py:341-454).
+ * rac_det_pack_fwd: the ConvLSTM input of DeterministicConvModel in one launch, out [B][HW][Gp]:
+ *   channels [0, g) = enc[b][p][:]; g + ch (ch 0, 1) = ba[ch*HW + p] + sum_k wa[ch*HW + p][k] * action[b][k]
+ *   (action_encoder(a).view(B, 2, h, w), dynamics.py:446); g + 2 + ch the same of ws / bs / state (state NULL: zeros);
+ *   everything from g + 4 up to the padded width Gp is zero.  g % 4 == 0, Gp % 4 == 0, Gp >= g + 4.
+ *   wa is the nn.Linear weight [2*HW][A] (row-major), ws [2*HW][R].  out_amax: as everywhere (nullable).
+ * rac_det_pack_bwd: from dout [B][HW][Gp]: denc[b][p][0:g] = dout[b][p][0:g] (nullable);
+ *   dwa[o][k] += sum_b dout[b][p][g + ch] * action[b][k], dba[o] += sum_b dout[b][p][g + ch] with o = ch*HW + p, and the
+ *   same of the state lanes into dws / dbs (each pair nullable).  Every sum is one thread's, b ascending: no atomics, the
+ *   same bits on every run.  Action and state are data: no gradient. */
+int rac_det_pack_fwd(const float* enc, int32_t g, const float* action, int32_t A, const float* wa, const float* ba,
+                     const float* state, int32_t R, const float* ws, const float* bs, float* out, int32_t Gp, int32_t B,
+                     int32_t HW, uint32_t* out_amax, void* stream);
+int rac_det_pack_bwd(const float* dout, int32_t Gp, int32_t g, const float* action, int32_t A, const float* state,
+                     int32_t R, float* denc, float* dwa, float* dba, float* dws, float* dbs, int32_t B, int32_t HW,
+                     void* stream);
+/* CopyModel (dynamics.py:341-357): out[b][c][p] = next_mask[b][p] != 0 ? next_image[b][c][p] : image[b][c][p] on
+ * (B, 3, H, W) planes, the (B, 1, H, W) mask broadcast over the channels */
+int rac_copy_baseline(const float* image, const float* next_image, const float* next_mask, float* out, int32_t B,
+                      int32_t HW, void* stream);
+
 /* Reconstruction losses + logging metrics in one pass (losses.py:11-78, trainer.py:149-161,426-452).
  * kind: 0 mse, 1 l1, 2 dontcare_mse, 3 dontcare_l1.  out[0] = loss, out[1] = robot_mse, out[2] = world_mse
  * (out[1..2] only when mask != NULL).  per_sample = workspace fp32 [B][8]. */

@@ -14,6 +14,10 @@ Differences that are deliberate and invisible to callers:
     passes produce identical activations, so the encoder runs once; BatchNorm
     running stats receive the two momentum updates and the gradient of both uses
     of `h` flows through the single pass.
+
+The deterministic baselines of the reference's `--model det | copy` live here too
+(`DeterministicConvModel`, `CopyModel`, reference dynamics.py:341-454), on the same
+building blocks and the same flat-buffer base class (`_FlatModel`).
 """
 from __future__ import annotations
 
@@ -46,6 +50,15 @@ class _Conv(nn.Module):
         # ConvTranspose2d stores (cin, cout, k, k)
         self.weight = _cl_weight(cin, cout, k) if transposed else _cl_weight(cout, cin, k)
         self.bias = nn.Parameter(torch.empty(cout)) if bias else None
+
+
+class _Linear(nn.Module):
+    """Parameter holder named like nn.Linear (`weight` (out, in), `bias`)."""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin))
+        self.bias = nn.Parameter(torch.empty(cout))
 
 
 class _BatchNorm(nn.Module):
@@ -287,46 +300,21 @@ class _GaussianConvLSTM(_ConvLSTM):
         return mu, logvar
 
 
-class SVGConvModel(nn.Module):
-    """Conv SVG LSTM predictor (reference dynamics.py:457-644) on hand-written gfx950 kernels."""
+class _FlatModel(nn.Module):
+    """What the models on librac_hip.so share: every parameter is a view of ONE flat fp32 buffer (its gradient of
+    another) for the fused optimiser steps and the reducers of optim.py / trainer.py, BatchNorm bookkeeping, the
+    state-dict hooks and the encoder pass with its waits for an optimiser update still in flight."""
 
-    def __init__(self, config):
+    def __init__(self):
         super().__init__()
-        self._config = cf = config
-        self._device = config.device
-        self._image_width = cf.image_width
-        self._image_height = cf.image_height
-        self.eps_source = None  # optional callable(shape_bzhw) -> N(0,1) tensor; tests inject the reference's draws
-        self.sequence_batched = None  # forward_sequence_maps: (mu, logvar, mu_p, logvar_p) over all T*B samples, if batched
-        self.used_recurrent_core = False  # did the last forward_sequence_maps take ops.RecurrentCore?
         self._flat = self._flat_grad = None
-        if cf.image_width not in (64, 128):  # dynamics.py:470-473
-            raise ValueError
-        enc_c = cf.channels
-        if cf.model_use_mask:
-            enc_c += 1 + (1 if cf.model_use_future_mask else 0)
-        if getattr(cf, "model_use_heatmap", False):
-            enc_c += 1 + (1 if getattr(cf, "model_use_future_heatmap", False) else 0)
-        g, z, A, R = cf.g_dim, cf.z_dim, cf.action_dim, cf.robot_dim
-        use_r, use_rn = cf.model_use_robot_state, cf.model_use_future_robot_state
-        extra = (R if use_r else 0) + (R if use_rn else 0)
-        self.encoder = _Encoder(g, enc_c)
-        self.frame_pred_input_conv = _Conv(g + A + z + extra, g, 3)
-        self.frame_predictor = _ConvLSTM(cf, g)
-        self.posterior_input_conv = _Conv(g + (R if use_r else 0), g, 3)
-        self.prior_input_conv = _Conv(g + A + extra, g, 3)
-        self.posterior = _GaussianConvLSTM(cf, g, z)
-        self.prior = _GaussianConvLSTM(cf, g, z)
-        self.decoder = _Decoder(g, cf.channels + 1)
-        self.reset_parameters()
-        self.to(self._device)
 
     # ------------------------------------------------------------------ params
     def reset_parameters(self):
         """init_weights (base.py:26-36): conv W ~ N(0, 0.02), b = 0; BatchNorm gamma ~ N(1, 0.02), beta = 0."""
         with torch.no_grad():
             for m in self.modules():
-                if isinstance(m, _Conv):
+                if isinstance(m, (_Conv, _Linear)):
                     m.weight.normal_(0.0, 0.02)
                     if m.bias is not None:
                         m.bias.zero_()
@@ -430,16 +418,115 @@ class SVGConvModel(nn.Module):
         ops.param_wait()
         self._flush_bn_counters()
         sd = super().state_dict(*a, **k)
+        return self._export_state(sd)
+
+    def _export_state(self, sd):
+        """Hook: storage -> the reference's keys / shapes (a model that stores some parameters at a padded width)."""
+        return sd
+
+    def _import_state(self, sd):
+        """Hook: the reference's keys / shapes -> what the parameters are stored as."""
         return sd
 
     def load_state_dict(self, state_dict, strict: bool = True, **k):
-        out = super().load_state_dict(state_dict, strict=strict, **k)
+        out = super().load_state_dict(self._import_state(state_dict), strict=strict, **k)
         for m in self.modules():
             if isinstance(m, _VggLayer):
                 m._folded = None
             if isinstance(m, _BatchNorm):
                 m.pending_updates = 0
         return out
+
+    # ---------------------------------------------------------------- encoder
+    def _encoder_extent(self) -> int:
+        """Flat-buffer element index behind the encoder's last parameter (the encoder is registered first)."""
+        ext = getattr(self, "_enc_extent", None)
+        if ext is None or ext[0] is not self._flat:  # (cached per flat buffer: walking the modules costs 50 us per call)
+            ext = self._enc_extent = (self._flat, max(p._rac_off + p.numel() for p in self.encoder.parameters()))
+        return ext[1]
+
+    def _encode(self, image, mask, heatmap, zero_mask, n_updates, groups, staged=False):
+        """`staged`: the caller waits for the later parameter groups itself (forward_sequence_maps: the recurrent core takes
+        its chains' weights as they arrive); otherwise everything is waited for behind the encoder."""
+        gate = ops.PARAM_GATE  # an optimiser update still in flight: optim.ShardedAdam's all-gather, FusedAdam's late groups
+        if gate is not None and getattr(gate, "_model", self) is not self:
+            gate.wait_params()  # another model's optimiser (a previous trainer of this process): let it land and drop it
+            gate = ops.PARAM_GATE = None
+        if gate is not None:
+            gate.wait_params(upto=self._encoder_extent())
+        out = self._encode_now(image, mask, heatmap, zero_mask, n_updates, groups)
+        if gate is not None:
+            if staged and hasattr(gate, "wait_for"):
+                gate.wait_for(self.prior_input_conv.weight)  # the first late group, under the encoder's kernels
+            else:
+                gate.wait_params()  # everything behind the encoder's parameters: waited for under the encoder's kernels
+        return out
+
+    def _encode_now(self, image, mask, heatmap, zero_mask, n_updates, groups):
+        cf = self._config
+        image = image.contiguous()
+        mask_planes = None
+        if getattr(cf, "model_use_heatmap", False):
+            mask_planes = heatmap
+        if cf.model_use_mask:
+            mask_planes = mask if mask_planes is None else torch.cat([mask_planes, mask], 1)
+        if mask_planes is not None:
+            mask_planes = mask_planes.contiguous()
+        zm = None if zero_mask is None else zero_mask.contiguous()
+        first = self.encoder.c1[0]
+        if (not self.training and not torch.is_grad_enabled() and ops.SPLIT_GEMM
+                and ops.first_layer_ok(image, mask_planes, first.main[0].weight)):
+            # frozen model: the first layer reads the planes directly (no packed, 32-channel-padded input tensor)
+            scale, shift = first.folded()
+            x1 = ops.first_layer_frozen(image, zm, mask_planes, first.main[0].weight, scale, shift)
+            return self.encoder(x1, n_updates, groups, first_done=True)
+        if (self.training and torch.is_grad_enabled() and ops.first_layer_train_ok(image, mask_planes, first.main[0].weight)
+                and (image.shape[0] * image.shape[-2] * image.shape[-1]) % groups == 0):
+            # training, frames are data: the first layer reads the planes on the matrix pipe (ops.FirstVggLayer)
+            bn = first.main[1]
+            bn.pending_updates += n_updates * groups
+            x1 = ops.FirstVggLayer.apply(image, zm, mask_planes, first.main[0].weight, bn.weight, bn.bias, bn.running_mean,
+                                         bn.running_var, n_updates, groups)
+            return self.encoder(x1, n_updates, groups, first_done=True)
+        # one whole 32-channel chunk (zero padded) where the first layer can take the split-precision kernels
+        H, W = image.shape[-2], image.shape[-1]
+        pad_to = 32 if (ops.SPLIT_GEMM and ops.split_supported(H, W, 3, 32, 64)) else 0
+        x_in = ops.PackInput.apply(image, None if zero_mask is None else zero_mask.contiguous(), mask_planes, pad_to)
+        return self.encoder(x_in, n_updates, groups)
+
+
+class SVGConvModel(_FlatModel):
+    """Conv SVG LSTM predictor (reference dynamics.py:457-644) on hand-written gfx950 kernels."""
+
+    def __init__(self, config):
+        super().__init__()
+        self._config = cf = config
+        self._device = config.device
+        self._image_width = cf.image_width
+        self._image_height = cf.image_height
+        self.eps_source = None  # optional callable(shape_bzhw) -> N(0,1) tensor; tests inject the reference's draws
+        self.sequence_batched = None  # forward_sequence_maps: (mu, logvar, mu_p, logvar_p) over all T*B samples, if batched
+        self.used_recurrent_core = False  # did the last forward_sequence_maps take ops.RecurrentCore?
+        if cf.image_width not in (64, 128):  # dynamics.py:470-473
+            raise ValueError
+        enc_c = cf.channels
+        if cf.model_use_mask:
+            enc_c += 1 + (1 if cf.model_use_future_mask else 0)
+        if getattr(cf, "model_use_heatmap", False):
+            enc_c += 1 + (1 if getattr(cf, "model_use_future_heatmap", False) else 0)
+        g, z, A, R = cf.g_dim, cf.z_dim, cf.action_dim, cf.robot_dim
+        use_r, use_rn = cf.model_use_robot_state, cf.model_use_future_robot_state
+        extra = (R if use_r else 0) + (R if use_rn else 0)
+        self.encoder = _Encoder(g, enc_c)
+        self.frame_pred_input_conv = _Conv(g + A + z + extra, g, 3)
+        self.frame_predictor = _ConvLSTM(cf, g)
+        self.posterior_input_conv = _Conv(g + (R if use_r else 0), g, 3)
+        self.prior_input_conv = _Conv(g + A + extra, g, 3)
+        self.posterior = _GaussianConvLSTM(cf, g, z)
+        self.prior = _GaussianConvLSTM(cf, g, z)
+        self.decoder = _Decoder(g, cf.channels + 1)
+        self.reset_parameters()
+        self.to(self._device)
 
     # ------------------------------------------------------------------ state
     def init_hidden(self, batch_size=None):
@@ -605,13 +692,6 @@ class SVGConvModel(nn.Module):
         """`forward_sequence_maps` needs per-step row ranges that are whole 128-row tiles at every resolution."""
         return self.training and bool(self._config.last_frame_skip) and (batch * (height // 8) * (width // 8)) % 128 == 0
 
-    def _encoder_extent(self) -> int:
-        """Flat-buffer element index behind the encoder's last parameter (the encoder is registered first)."""
-        ext = getattr(self, "_enc_extent", None)
-        if ext is None or ext[0] is not self._flat:  # (cached per flat buffer: walking the modules costs 50 us per call)
-            ext = self._enc_extent = (self._flat, max(p._rac_off + p.numel() for p in self.encoder.parameters()))
-        return ext[1]
-
     def late_update_groups(self):
         """Parameters behind the encoder's in the order a teacher-forced window first reads them (optim.FusedAdam updates
         its late weights in these groups): the prior's chain (+ both input convs, which run right behind the encoder), the
@@ -620,55 +700,6 @@ class SVGConvModel(nn.Module):
                                                                                     if hasattr(c, "gates")]
         second = [c.gates.weight for c in self.posterior.lstm if hasattr(c, "gates")]
         return [first, second]
-
-    def _encode(self, image, mask, heatmap, zero_mask, n_updates, groups, staged=False):
-        """`staged`: the caller waits for the later parameter groups itself (forward_sequence_maps: the recurrent core takes
-        its chains' weights as they arrive); otherwise everything is waited for behind the encoder."""
-        gate = ops.PARAM_GATE  # an optimiser update still in flight: optim.ShardedAdam's all-gather, FusedAdam's late groups
-        if gate is not None and getattr(gate, "_model", self) is not self:
-            gate.wait_params()  # another model's optimiser (a previous trainer of this process): let it land and drop it
-            gate = ops.PARAM_GATE = None
-        if gate is not None:
-            gate.wait_params(upto=self._encoder_extent())
-        out = self._encode_now(image, mask, heatmap, zero_mask, n_updates, groups)
-        if gate is not None:
-            if staged and hasattr(gate, "wait_for"):
-                gate.wait_for(self.prior_input_conv.weight)  # the first late group, under the encoder's kernels
-            else:
-                gate.wait_params()  # everything behind the encoder's parameters: waited for under the encoder's kernels
-        return out
-
-    def _encode_now(self, image, mask, heatmap, zero_mask, n_updates, groups):
-        cf = self._config
-        image = image.contiguous()
-        mask_planes = None
-        if getattr(cf, "model_use_heatmap", False):
-            mask_planes = heatmap
-        if cf.model_use_mask:
-            mask_planes = mask if mask_planes is None else torch.cat([mask_planes, mask], 1)
-        if mask_planes is not None:
-            mask_planes = mask_planes.contiguous()
-        zm = None if zero_mask is None else zero_mask.contiguous()
-        first = self.encoder.c1[0]
-        if (not self.training and not torch.is_grad_enabled() and ops.SPLIT_GEMM
-                and ops.first_layer_ok(image, mask_planes, first.main[0].weight)):
-            # frozen model: the first layer reads the planes directly (no packed, 32-channel-padded input tensor)
-            scale, shift = first.folded()
-            x1 = ops.first_layer_frozen(image, zm, mask_planes, first.main[0].weight, scale, shift)
-            return self.encoder(x1, n_updates, groups, first_done=True)
-        if (self.training and torch.is_grad_enabled() and ops.first_layer_train_ok(image, mask_planes, first.main[0].weight)
-                and (image.shape[0] * image.shape[-2] * image.shape[-1]) % groups == 0):
-            # training, frames are data: the first layer reads the planes on the matrix pipe (ops.FirstVggLayer)
-            bn = first.main[1]
-            bn.pending_updates += n_updates * groups
-            x1 = ops.FirstVggLayer.apply(image, zm, mask_planes, first.main[0].weight, bn.weight, bn.bias, bn.running_mean,
-                                         bn.running_var, n_updates, groups)
-            return self.encoder(x1, n_updates, groups, first_done=True)
-        # one whole 32-channel chunk (zero padded) where the first layer can take the split-precision kernels
-        H, W = image.shape[-2], image.shape[-1]
-        pad_to = 32 if (ops.SPLIT_GEMM and ops.split_supported(H, W, 3, 32, 64)) else 0
-        x_in = ops.PackInput.apply(image, None if zero_mask is None else zero_mask.contiguous(), mask_planes, pad_to)
-        return self.encoder(x_in, n_updates, groups)
 
     def _embed(self, conv, vs, h, z):
         """conv(cat[tile(vs), h, z]) (dynamics.py:591-607,634-640); the frozen model's conv reads h in place (no
@@ -715,3 +746,192 @@ class SVGConvModel(nn.Module):
         frame_in = self._embed(f, [v for v in (a, r, r_next) if v is not None], h, z)
         h_pred = self.frame_predictor(frame_in)
         return h_pred, mu, logvar, mu_p, logvar_p
+
+
+# --------------------------------------------------------------------------- #
+# the deterministic baselines (reference dynamics.py:341-454)
+# --------------------------------------------------------------------------- #
+DET_WIDTH_MULTIPLE = 64  # the two-source split weight gradient needs its first source's width % 64 == 0 (ops.wgrad_split_ok)
+
+
+def det_padded_width(width: int) -> int:
+    """Stored ConvLSTM width of DeterministicConvModel: g + 2 / g + 4 rounded up to what every split kernel admits."""
+    return -(-width // DET_WIDTH_MULTIPLE) * DET_WIDTH_MULTIPLE
+
+
+def _gate_blocks(t: torch.Tensor, width: int):
+    """A ConvLSTM gate parameter as its blocks: weight (4w, 2w, k, k) -> (4, w, 2, w, k, k) (gate, channel, input half,
+    channel), bias (4w,) -> (4, w).  A view, whatever the strides: only whole dimensions are split."""
+    if t.dim() == 1:
+        return t.view(4, width)
+    return t.view(4, width, 2, width, t.shape[2], t.shape[3])
+
+
+def pad_gate_param(t: torch.Tensor, width: int, padded: int) -> torch.Tensor:
+    """Reference gate weight (4w, 2w, k, k) / bias (4w,) -> zero-padded storage (4p, 2p, k, k) / (4p,): each of the four
+    gate blocks and each of the two input halves is padded on its own."""
+    if t.dim() == 1:
+        out = t.new_zeros(4, padded)
+        out[:, :width] = _gate_blocks(t.contiguous(), width)
+        return out.reshape(4 * padded)
+    k = t.shape[2]
+    out = t.new_zeros(4, padded, 2, padded, k, k)
+    out[:, :width, :, :width] = _gate_blocks(t.contiguous(), width)
+    return out.reshape(4 * padded, 2 * padded, k, k)
+
+
+def unpad_gate_param(t: torch.Tensor, width: int, padded: int) -> torch.Tensor:
+    """The reference-shaped copy of a stored gate weight / bias (inverse of pad_gate_param)."""
+    b = _gate_blocks(t, padded)
+    if t.dim() == 1:
+        return b[:, :width].reshape(4 * width)
+    return b[:, :width, :, :width].reshape(4 * width, 2 * width, t.shape[2], t.shape[3])
+
+
+class DeterministicConvModel(_FlatModel):
+    """Deterministic Conv LSTM predictor (reference dynamics.py:363-454) on the same kernels as SVGConvModel: VGG encoder,
+    one ConvLSTM over [h | action_encoder(a) | state_encoder(r)], VGG decoder; no prior, no posterior.
+
+    The ConvLSTM's width g + 2 (+ 2 with the robot state) is no width any split-precision kernel admits, so the ConvLSTM
+    and the decoder's first conv are STORED at `padded_width` (a multiple of 64) with every padded row, column and bias
+    zero.  A padded channel's gates are 0, so its c and h stay 0; its gradient rows and columns are exact zeros; Adam,
+    RMSprop and SGD leave an exact zero with a zero gradient at zero.  `state_dict()` hands out the reference's shapes (as
+    copies), `load_state_dict()` takes them and re-zeroes the padding."""
+
+    def __init__(self, config):
+        super().__init__()
+        self._config = cf = config
+        self._device = config.device
+        self._image_width = cf.image_width
+        self._image_height = cf.image_height
+        if cf.image_width != 64:  # dynamics.py:378-381
+            raise ValueError
+        g = cf.g_dim
+        use_r = bool(cf.model_use_robot_state)
+        self.width = g + 2 + (2 if use_r else 0)
+        if getattr(cf, "lstm_group_norm", False):
+            # the reference cannot build this either: NormConvLSTMCell's nn.GroupNorm(16, width) raises (lstm.py:151-198)
+            raise ValueError(f"--model det with --lstm_group_norm True: num_channels must be divisible by num_groups "
+                             f"(GroupNorm(16, {self.width}), as in the reference)")
+        if g % 4:
+            raise ValueError(f"--model det: g_dim {g} must be a multiple of 4 on the HIP path")
+        self.padded_width = gp = det_padded_width(self.width)
+        enc_c = cf.channels
+        if cf.model_use_mask:
+            enc_c += 1 + (1 if cf.model_use_future_mask else 0)
+        hw = (cf.image_height // 8) * (cf.image_width // 8)
+        self.encoder = _Encoder(g, enc_c)
+        self.action_encoder = nn.ModuleList([_Linear(cf.action_dim, 2 * hw)])
+        if use_r:
+            self.state_encoder = nn.ModuleList([_Linear(cf.robot_dim, 2 * hw)])
+        self.frame_predictor = _ConvLSTM(cf, gp)
+        self.decoder = _Decoder(gp, cf.channels + 1)
+        self.reset_parameters()
+        self._zero_padding()
+        self.to(self._device)
+
+    # ---------------------------------------------------------------- padding
+    def _padded_params(self):
+        """(state-dict key, parameter, kind) of everything stored wider than the reference's shape."""
+        out = []
+        for i, cell in enumerate(self.frame_predictor.lstm):
+            out.append((f"frame_predictor.lstm.{i}.gates.weight", cell.gates.weight, "gate"))
+            out.append((f"frame_predictor.lstm.{i}.gates.bias", cell.gates.bias, "gate"))
+        out.append(("decoder.upc2.0.main.0.weight", self.decoder.upc2[0].main[0].weight, "cin"))
+        return out
+
+    def _zero_padding(self):
+        w, gp = self.width, self.padded_width
+        with torch.no_grad():
+            for _, p, kind in self._padded_params():
+                if kind == "cin":
+                    p.data[:, w:] = 0
+                    continue
+                b = _gate_blocks(p.data, gp)
+                b[:, w:] = 0
+                if p.dim() == 4:
+                    b[:, :, :, w:] = 0
+
+    def padding_mask(self) -> torch.Tensor:
+        """Bool mask over the flat parameter buffer (the gradient and optimiser-state buffers share its layout): True at
+        every padding element of the padded parameters."""
+        if self._flat is None:
+            self._flatten()
+        w, gp = self.width, self.padded_width
+        mask = torch.zeros(self._flat.numel(), dtype=torch.bool, device=self._flat.device)
+        for _, p, kind in self._padded_params():
+            v = torch.as_strided(mask, p.shape, p.stride(), p._rac_off)
+            if kind == "cin":
+                v[:, w:] = True
+                continue
+            b = _gate_blocks(v, gp)
+            b[:, w:] = True
+            if p.dim() == 4:
+                b[:, :, :, w:] = True
+        return mask
+
+    def _export_state(self, sd):
+        w, gp = self.width, self.padded_width
+        for key, _, kind in self._padded_params():
+            t = sd[key].detach()
+            sd[key] = t[:, :w].clone() if kind == "cin" else unpad_gate_param(t, w, gp)
+        return sd
+
+    def _import_state(self, sd):
+        w, gp = self.width, self.padded_width
+        sd = dict(sd)
+        for key, p, kind in self._padded_params():
+            if key not in sd:
+                continue
+            t = sd[key]
+            if kind == "cin":
+                want = (p.shape[0], w, 3, 3)
+            else:
+                want = (4 * w,) if p.dim() == 1 else (4 * w, 2 * w) + tuple(p.shape[2:])
+            if tuple(t.shape) != tuple(want):
+                raise RuntimeError(f"{key}: expected the reference shape {tuple(want)}, got {tuple(t.shape)}")
+            if kind == "cin":
+                full = t.new_zeros((t.shape[0], gp, 3, 3))
+                full[:, :w] = t
+                sd[key] = full
+            else:
+                sd[key] = pad_gate_param(t, w, gp)
+        return sd
+
+    # ---------------------------------------------------------------- forward
+    def init_hidden(self, batch_size=None):
+        """Initialize the recurrent states by batch size (dynamics.py:416-420)."""
+        self.frame_predictor.hidden = self.frame_predictor.init_hidden(batch_size)
+
+    def forward(self, image, mask, robot, action, skip=None):
+        """Predict the next frame (same contract as reference dynamics.py:422-454): (x_pred (B,4,H,W), skip list)."""
+        x4, skip_maps = self.forward_maps(image, mask, robot, action,
+                                          None if skip is None else [s.permute(0, 2, 3, 1).contiguous() for s in skip])
+        v = ops.to_planes_view
+        return v(x4), [v(s) for s in skip_maps]
+
+    def forward_maps(self, image, mask, robot, action, skip=None, zero_mask=None):
+        """`forward` on NHWC maps; `zero_mask` fuses zero_robot_region(mask, image) into the input packing."""
+        h, curr_skip = self._encode(image, mask, None, zero_mask, 1, 1)
+        if skip is None:
+            skip = curr_skip
+        a_enc = self.action_encoder[0]
+        if self._config.model_use_robot_state:
+            s_enc = self.state_encoder[0]
+            state = ops.DetPack.apply(h, action, a_enc.weight, a_enc.bias, robot, s_enc.weight, s_enc.bias,
+                                      self.padded_width)
+        else:
+            state = ops.DetPack.apply(h, action, a_enc.weight, a_enc.bias, None, None, None, self.padded_width)
+        h_pred = self.frame_predictor(state)
+        return self.decoder(h_pred, skip), skip
+
+
+class CopyModel(nn.Module):
+    """Baseline that copies the previous frame's world pixels (reference dynamics.py:341-360); evaluation only."""
+
+    @torch.no_grad()
+    def forward(self, image, mask, next_image, next_mask):
+        return ops.copy_baseline(image, next_image, next_mask)
+
+    def init_hidden(self, batch_size=None):
+        pass

@@ -3089,6 +3089,65 @@ def first_layer_frozen(img, zero_mask, mask, weight, scale, shift) -> torch.Tens
     return tag_amax(out, slot)
 
 
+class DetPack(torch.autograd.Function):
+    """DeterministicConvModel's ConvLSTM input (dynamics.py:445-451) at the padded width `gp`:
+    [h | action_encoder(a).view(B, 2, H, W) | state_encoder(r).view(B, 2, H, W) | zeros], one launch each way.
+    Gradients flow to the encoder map; the Linears' weight / bias gradients are accumulated into their .grad in a fixed
+    order (no atomics); action and state are data."""
+
+    @staticmethod
+    def forward(ctx, h, action, w_a, b_a, state, w_s, b_s, gp):
+        _require_cuda(h)
+        B, H, W, g = h.shape
+        HW = H * W
+        h, action = h.contiguous(), action.contiguous()
+        state = None if state is None else state.contiguous()
+        if tuple(w_a.shape) != (2 * HW, action.shape[1]) or not w_a.is_contiguous():
+            raise _lib.RacError(f"action_encoder weight {tuple(w_a.shape)} does not fit a {H}x{W} map")
+        if state is not None and (tuple(w_s.shape) != (2 * HW, state.shape[1]) or not w_s.is_contiguous()):
+            raise _lib.RacError(f"state_encoder weight {tuple(w_s.shape)} does not fit a {H}x{W} map")
+        out = torch.empty((B, H, W, gp), device=h.device, dtype=torch.float32)
+        slot = amax_slot(h.device)
+        call("rac_det_pack_fwd", ptr(h), g, ptr(action), action.shape[1], ptr(w_a), ptr(b_a), ptr(state),
+             state.shape[1] if state is not None else 0, ptr(w_s) if state is not None else None,
+             ptr(b_s) if state is not None else None, ptr(out), gp, B, HW, ptr(slot), stream_ptr())
+        tag_amax(out, slot)
+        ctx.save_for_backward(action, state, w_a, b_a, w_s, b_s)
+        ctx.g = g
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        action, state, w_a, b_a, w_s, b_s = ctx.saved_tensors
+        dout = dout.contiguous()
+        B, H, W, gp = dout.shape
+        g = ctx.g
+        dh = torch.empty((B, H, W, g), device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        lin_a = w_a.requires_grad
+        lin_s = state is not None and w_s.requires_grad
+        if dh is not None or lin_a or lin_s:
+            call("rac_det_pack_bwd", ptr(dout), gp, g, ptr(action), action.shape[1], ptr(state),
+                 state.shape[1] if state is not None else 0, ptr(dh),
+                 ptr(grad_buffer(w_a)) if lin_a else None, ptr(grad_buffer(b_a)) if lin_a else None,
+                 ptr(grad_buffer(w_s)) if lin_s else None, ptr(grad_buffer(b_s)) if lin_s else None, B, H * W, stream_ptr())
+        return dh, None, None, None, None, None, None, None
+
+
+def copy_baseline(image: torch.Tensor, next_image: torch.Tensor, next_mask: torch.Tensor) -> torch.Tensor:
+    """CopyModel (dynamics.py:341-357): the next frame's robot pixels, the current frame's world pixels."""
+    _require_cuda(image)
+    B, Cc, H, W = image.shape
+    if Cc != 3 or tuple(next_image.shape) != (B, 3, H, W) or tuple(next_mask.shape) != (B, 1, H, W):
+        raise _lib.RacError(f"copy_baseline: (B,3,H,W) frames and a (B,1,H,W) mask, got {tuple(image.shape)}, "
+                            f"{tuple(next_image.shape)}, {tuple(next_mask.shape)}")
+    image = image.detach().to(torch.float32).contiguous()
+    next_image = next_image.detach().to(torch.float32).contiguous()
+    next_mask = next_mask.detach().to(torch.float32).contiguous()
+    out = torch.empty_like(image)
+    call("rac_copy_baseline", ptr(image), ptr(next_image), ptr(next_mask), ptr(out), B, H * W, stream_ptr())
+    return out
+
+
 class ZeroRegion(torch.autograd.Function):
     """zero_robot_region (src/utils/image.py:5-19), out of place."""
 

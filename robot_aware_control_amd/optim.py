@@ -16,6 +16,20 @@ import torch.distributed as dist
 from . import _lib, ops
 
 
+def _require_storage_shapes(opt, names):
+    """A state dict's per-parameter tensors must have the shapes the parameters are STORED with (a model that pads some
+    of them -- model.DeterministicConvModel -- keeps its optimiser state at storage shapes): checked for every entry
+    before the first copy, so that a mismatch raises with nothing loaded."""
+    for p in opt.param_groups[0]["params"]:
+        st = opt.state.get(p) or {}
+        for name in names:
+            t = st.get(name)
+            if t is not None and tuple(t.shape) != tuple(p.shape):
+                opt.state.clear()
+                raise ValueError("optimizer state %r has shape %s, the parameter is stored as %s"
+                                 % (name, tuple(t.shape), tuple(p.shape)))
+
+
 class FusedAdam(torch.optim.Optimizer):
     # The pass is bound by HBM (8.6 GB per step at g512: ~1.7 ms); the forward pass that follows starts with the encoder's
     # many small launches (2.2 ms, bound by latency, reading only the encoder's parameters).  With `overlap_next_forward` the
@@ -145,6 +159,7 @@ class FusedAdam(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         self.wait_params()
         super().load_state_dict(state_dict)
+        _require_storage_shapes(self, ("exp_avg", "exp_avg_sq"))
         steps = 0
         for p, mv, vv in self._views():
             st = self.state.get(p)
@@ -425,6 +440,7 @@ class FusedRMSprop(_FlatOptimizer):
         super().load_state_dict(state_dict)
         self._check(self.param_groups[0])
         names = [n for n in self._names(self.param_groups[0]) if n]
+        _require_storage_shapes(self, names)
         steps = 0
         for p, views in self._views(names):
             st = self.state.get(p)
@@ -466,6 +482,7 @@ class FusedSGD(_FlatOptimizer):
         super().load_state_dict(state_dict)
         self._check(self.param_groups[0])
         have = []
+        _require_storage_shapes(self, ("momentum_buffer",))
         if self.param_groups[0]["momentum"] != 0:
             for p, (view,) in self._views(["momentum_buffer"]):
                 buf = (self.state.get(p) or {}).get("momentum_buffer")

@@ -1,5 +1,5 @@
-"""PredictionTrainer: the SVG train step on librac_hip.so, API-compatible with the reference
-`src/prediction/trainer.py` (`PredictionTrainer(config)`, `_train_step`, `_train_video`, `train`,
+"""PredictionTrainer: the SVG train step (and the `--model det | copy` baselines) on librac_hip.so, API-compatible
+with the reference `src/prediction/trainer.py` (`PredictionTrainer(config)`, `_train_step`, `_train_video`, `train`,
 checkpoint format `{"model","optimizer","step"}`, ckpt_{step}.pt discovery).
 
 MI355X-first differences:
@@ -21,7 +21,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops, parallel_env
-from .model import SVGConvModel
+from .model import CopyModel, DeterministicConvModel, SVGConvModel
 from .optim import FusedAdam, ShardedAdam, make_optimizer
 
 # teacher-forced windows run the encoder / decoder once over all time steps (RAC_SEQUENCE_PATH=0: step by step)
@@ -157,9 +157,17 @@ class PredictionTrainer(object):
 
     # ------------------------------------------------------------------ setup
     def _init_models(self, cf):
-        if cf.model != "svg":  # trainer.py:99-107: det / copy / cdna_det are outside the accelerated path
-            raise ValueError(f"{cf.model}: only --model svg is built on the HIP path")
-        self.model = SVGConvModel(cf).to(self._device)
+        # trainer.py:99-107: svg, det, copy (cdna_det is the reference's ValueError here too)
+        if cf.model == "svg":
+            self.model = SVGConvModel(cf).to(self._device)
+        elif cf.model == "det":
+            self.model = DeterministicConvModel(cf).to(self._device)
+        elif cf.model == "copy":
+            self.model = CopyModel()  # no parameters, no optimiser (trainer.py:103-105)
+            self.optimizer = None
+            return
+        else:
+            raise ValueError(f"{cf.model}: --model svg, det and copy are built on the HIP path")
         if _dist_on():  # identical initial weights on every rank
             dist.broadcast(self.model.flat_parameters()[0], src=0)
         # --optimizer adam | rmsprop | sgd (trainer.py:109-122); anything else is the reference's ValueError
@@ -257,11 +265,14 @@ class PredictionTrainer(object):
         cf = self._config
         dev = self._device
         f32 = torch.float32
+        det = cf.model == "det"  # trainer.py:383-384: no prior / posterior, no KL term, no heatmap input
+        if cf.model == "copy":
+            raise ValueError("--model copy has nothing to train (trainer.py:739-741: train() only evaluates it)")
         x = data["images"].to(dev, f32)
         states = data["states"].to(dev, f32)
         ac = data["actions"].to(dev, f32)
         mask = data["masks"].to(dev, f32)
-        heatmaps = data["heatmaps"].to(dev, f32) if getattr(cf, "model_use_heatmap", False) else None
+        heatmaps = data["heatmaps"].to(dev, f32) if getattr(cf, "model_use_heatmap", False) and not det else None
         robot_name = np.array(data["robot"])
         all_robots = sorted(set(robot_name))
         batch_weight = None
@@ -309,7 +320,8 @@ class PredictionTrainer(object):
                            for i in range(2, n_steps + 1)]
         H, W = x.shape[-2], x.shape[-1]
         sequence_taken = False
-        if SEQUENCE_PATH and all(truths) and self.model.sequence_ok(bs, H, W) and x.shape[1] == bs:
+        # (the deterministic model always goes step by step: the time-batched window and the hand-scheduled core are SVG's)
+        if SEQUENCE_PATH and not det and all(truths) and self.model.sequence_ok(bs, H, W) and x.shape[1] == bs:
             sequence_taken = True
             # every input frame is ground truth: encoder and decoder run once over the whole window
             T = n_steps
@@ -355,12 +367,16 @@ class PredictionTrainer(object):
                 if heatmaps is not None:
                     hm_in = (torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap
                              else heatmaps[i - 1])
-                x4, curr_skip, mu, logvar, mu_p, logvar_p = self.model.forward_maps(
-                    x_j, m_in, r_in, hm_in, a_j, True, r_i, skip, zero_mask=m_j if dontcare else None)
+                mu = logvar = mu_p = logvar_p = None
+                if det:
+                    x4, curr_skip = self.model.forward_maps(x_j, m_in, r_j, a_j, skip, zero_mask=m_j if dontcare else None)
+                else:
+                    x4, curr_skip, mu, logvar, mu_p, logvar_p = self.model.forward_maps(
+                        x_j, m_in, r_in, hm_in, a_j, True, r_i, skip, zero_mask=m_j if dontcare else None)
                 x_pred = ops.Composite.apply(x4, x_j.contiguous())  # un-blacked x_j (trainer.py:406-407)
                 if i <= cf.n_past:
                     skip = curr_skip
-                add_losses(x_pred, i, mu, logvar, mu_p, logvar_p)
+                add_losses(x_pred, i, mu, logvar, mu_p, logvar_p, kl_here=not det)
         # the step's loss scalars are final once the forward pass is enqueued: start their device->host copy now (into
         # pinned memory) and collect it after the optimiser step is enqueued, so that the host never waits for the
         # backward pass or Adam (the reference likewise reads its losses before loss.backward(), trainer.py:433-458)
@@ -401,7 +417,8 @@ class PredictionTrainer(object):
             self._mark("allreduce_exposed")
         self.optimizer.step()
         self._mark("adam")
-        self.model.sequence_batched = None  # (graph references of this step)
+        if not det:
+            self.model.sequence_batched = None  # (graph references of this step)
 
         copied.synchronize()  # the one host wait of the step (normally already satisfied)
         vals = vals_host.tolist()
@@ -474,7 +491,8 @@ class PredictionTrainer(object):
         ac = data["actions"].to(dev, f32)
         true_masks = data["masks"].to(dev, f32)
         masks = data["pred_masks"].to(dev, f32)
-        heatmaps = data["heatmaps"].to(dev, f32) if getattr(cf, "model_use_heatmap", False) else None
+        svg = cf.model == "svg"  # det (trainer.py:628-629) and copy (:606-607) have no prior: no KL term, no heatmap
+        heatmaps = data["heatmaps"].to(dev, f32) if getattr(cf, "model_use_heatmap", False) and svg else None
         robot_name = np.array(data["robot"])
         all_robots = sorted(set(robot_name))
         bs = min(cf.test_batch_size, x.shape[1])
@@ -494,12 +512,18 @@ class PredictionTrainer(object):
             hm_in = None
             if heatmaps is not None:
                 hm_in = torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap else heatmaps[i - 1]
-            x4, curr_skip, mu, logvar, mu_p, logvar_p = self.model.forward_maps(
-                x_j, m_in, r_in, hm_in, a_j, True, r_i, skip, force_use_prior=True,
-                zero_mask=m_j if dontcare else None)
-            x_pred = ops.Composite.apply(x4, x_j.contiguous())
-            if i <= cf.n_past:
-                skip = curr_skip
+            if cf.model == "copy":
+                x_pred = self.model(x_j, m_j, x[i], m_i)  # on the rollout's masks (`pred_masks`)
+            else:
+                if svg:
+                    x4, curr_skip, mu, logvar, mu_p, logvar_p = self.model.forward_maps(
+                        x_j, m_in, r_in, hm_in, a_j, True, r_i, skip, force_use_prior=True,
+                        zero_mask=m_j if dontcare else None)
+                else:
+                    x4, curr_skip = self.model.forward_maps(x_j, m_in, r_j, a_j, skip, zero_mask=m_j if dontcare else None)
+                x_pred = ops.Composite.apply(x4, x_j.contiguous())
+                if i <= cf.n_past:
+                    skip = curr_skip
             tm = true_masks[i].contiguous()
             rec = self._recon_loss(x_pred, x[i].contiguous(), tm)
             log += [(f"{prefix}_recon_loss", rec[0]), (f"{prefix}_robot_loss", rec[1]), (f"{prefix}_world_loss", rec[2])]
@@ -514,8 +538,9 @@ class PredictionTrainer(object):
                     sub = ops.ReconLoss.apply(x_pred[idx].contiguous(), x[i][idx].contiguous(), tm[idx].contiguous(),
                                               None, 0, 0.0)
                     log += [(f"{prefix}_{r}_robot_loss", sub[1]), (f"{prefix}_{r}_world_loss", sub[2])]
-            kl = ops.KLLoss.apply(mu, logvar, mu_p, logvar_p, bs)
-            log.append((f"{prefix}_kld", kl[0]))
+            if svg:
+                kl = ops.KLLoss.apply(mu, logvar, mu_p, logvar_p, bs)
+                log.append((f"{prefix}_kld", kl[0]))
         vals = torch.stack([t.reshape(()) for _, t in log + klog]).cpu().tolist()
         losses = defaultdict(float)
         for (name, _), v in zip(log, vals[:len(log)]):
@@ -534,6 +559,8 @@ class PredictionTrainer(object):
         `data`: a time-first batch.  Returns the file name."""
         from PIL import Image
         cf = self._config
+        if cf.model != "svg":
+            raise NotImplementedError(f"plot() draws the svg model's prior samples; GIFs of --model {cf.model} are not built")
         dev, f32 = self._device, torch.float32
         b = min(data["images"].shape[1], 25)
         length = cf.n_past + cf.n_future if name in ("comparison", "train") else cf.n_eval
@@ -603,6 +630,8 @@ class PredictionTrainer(object):
         root, on the zero-shot transfer loader (`transfer/*`) as the reference does; with `--plot True` (this repo's
         switch, default off) a GIF of generations is written per epoch / evaluation (`plot`)."""
         cf = self._config
+        if cf.model == "copy":
+            return self.train_copy_baseline(test_loader=test_loader, transfer_loader=transfer_loader)
         self._step = self._load_checkpoint(cf.dynamics_model_ckpt)
         # this loop owns every reader of the parameters between two steps (forward passes and checkpoints, which wait):
         # the optimiser may finish the large weights' update under the next step's encoder (optim.FusedAdam)
@@ -611,7 +640,7 @@ class PredictionTrainer(object):
         if batch_generator is None:
             batch_generator, test_loader = self._setup_data()
             transfer_loader = transfer_loader or getattr(self, "transfer_loader", None)
-        plots = bool(getattr(cf, "plot", False)) and (not _dist_on() or dist.get_rank() == 0)
+        plots = bool(getattr(cf, "plot", False)) and cf.model == "svg" and (not _dist_on() or dist.get_rank() == 0)
 
         def evaluate(loader, name, epoch):
             from .data import process_batch
@@ -652,6 +681,34 @@ class PredictionTrainer(object):
         self.optimizer.wait_params()
         if ops.PARAM_GATE is self.optimizer:
             ops.PARAM_GATE = None
+        return info
+
+    def train_copy_baseline(self, train_loader=None, test_loader=None, transfer_loader=None):
+        """Metrics of the copy baseline over the train and test sets (trainer.py:794-827), and over a transfer loader if
+        the caller hands one in (the reference walks one for `--experiment train_sawyer_multiview` only).  Nothing is
+        trained or saved.  With --wandb every set is logged at steps 0 and 500000 (a horizontal line next to the trained
+        models' curves).  Returns the metrics."""
+        cf = self._config
+        self._step = 0  # (trainer.py:798 loads a checkpoint's step; a model without parameters has none)
+        if train_loader is None and test_loader is None:
+            if cf.data_root == "synthetic":
+                _, test_loader = self._setup_data()  # (the synthetic training stream has no end: the test set only)
+            else:
+                from . import data as D
+                train_loader, test_loader = D.create_loaders(cf)  # (the loaders themselves: no device prefetch thread)
+        info = {}
+        self.eval_history = []
+        for loader, name, training in ((train_loader, "train", True), (test_loader, "test", False),
+                                       (transfer_loader, "transfer", False)):
+            if loader is None:
+                continue
+            self.model.train(training)
+            part = self._compute_epoch_metrics(loader, name)
+            self.eval_history.append((0, part))
+            info.update(part)
+        if self._wandb is not None:
+            for step in (0, 500000):
+                self._wandb.log(info, step=step)
         return info
 
     def _setup_data(self):

@@ -1,2 +1,3 @@
-"""`from src.prediction.models.dynamics import SVGConvModel` (reference dynamics.py:457-644)."""
-from robot_aware_control_amd.model import SVGConvModel  # noqa: F401
+"""`from src.prediction.models.dynamics import SVGConvModel, DeterministicConvModel, CopyModel`
+(reference dynamics.py:457-644, :363-454, :341-360)."""
+from robot_aware_control_amd.model import CopyModel, DeterministicConvModel, SVGConvModel  # noqa: F401
