@@ -450,6 +450,23 @@ int rac_zero_region(const float* img, const float* mask, float* out, int32_t B, 
 int rac_composite_fwd(const float* x4, const float* prev, float* out, int32_t B, int32_t HW, void* stream);
 int rac_composite_bwd(const float* dout, const float* x4, const float* prev, float* dx4, float* dprev, int32_t B,
                       int32_t HW, void* stream);
+/* Everything behind the decoder in one rollout step of PredictionTrainer._predict_video (trainer.py:1317-1318,
+ * 1351-1355, 1398-1407), one launch:
+ *   pred[b][c][p] = (1-m)*prev[b][c][p] + m*x4[b][p][c], m = x4[b][p][3] -- rac_composite_fwd's expression, the same bits;
+ *   gen_u8  + b*image_stride : image b's (H, W, 3) uint8 frame of pred, b < n;
+ *   true_u8 + b*image_stride : likewise of target, b < nt only (true_u8 may be NULL: not written).
+ * The n images are n / nt sample groups over the same nt videos: image b reads target[b % nt] (nt, 3, H, W) and
+ * true_mask[b % nt] (nt, 1, H, W; fp32 0 / 1).  The caller passes the pointers to step t of (n, T, H, W, 3) /
+ * (nt, T, H, W, 3) video buffers and image_stride = T*H*W*3 bytes.
+ * x4 == NULL: pred is read, not written (--model copy: rac_copy_baseline made the frame), prev is ignored.
+ * uint8 value: 0 where true_mask != 0; elsewhere the fp32 product 255.0f * v truncated toward zero, which is what
+ * `(255 * x).numpy().astype(np.uint8)` gives for x in [0, 1] (no rounding, one multiply, no fused multiply-add).
+ * Outside [0, 1] numpy's cast is undefined: here the product is clamped to [0, 255] first and NaN gives 0.
+ * W % 4 == 0, image_stride % 4 == 0; float buffers 16-byte aligned, the uint8 pointers 4-byte aligned.  Every output
+ * element has exactly one writer (no atomics). */
+int rac_predict_frames(const float* x4, const float* prev, const float* target, const float* true_mask, float* pred,
+                       uint8_t* gen_u8, uint8_t* true_u8, int64_t image_stride, int32_t n, int32_t nt, int32_t H,
+                       int32_t W, void* stream);
 
 /* The deterministic baselines (dynamics.py:341-454).
  * rac_det_pack_fwd: the ConvLSTM input of DeterministicConvModel in one launch, out [B][HW][Gp]:

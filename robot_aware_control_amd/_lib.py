@@ -148,6 +148,7 @@ _SIGS = {
     "rac_zero_region": [vp, vp, vp, i32, i32, vp],
     "rac_composite_fwd": [vp, vp, vp, i32, i32, vp],
     "rac_composite_bwd": [vp, vp, vp, vp, vp, i32, i32, vp],
+    "rac_predict_frames": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
     "rac_det_pack_fwd": [vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp],
     "rac_det_pack_bwd": [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp],
     "rac_copy_baseline": [vp, vp, vp, vp, i32, i32, vp],

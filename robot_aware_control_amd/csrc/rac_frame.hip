@@ -291,6 +291,73 @@ __global__ void composite_bwd_kernel(const float* dout, const f32x4* x4, const f
   }
 }
 
+// ---- predict_video step tail ------------------------------------------------
+// uint8 of a [0, 1] value the way `(255 * x).numpy().astype(np.uint8)` makes it: ONE fp32 multiply (never contracted
+// into a neighbouring add), truncated toward zero.  Outside [0, 1] numpy's cast is undefined; here the product is
+// clamped to [0, 255] first and NaN gives 0 (fmaxf returns its non-NaN operand).
+__device__ __forceinline__ unsigned u8_of(float v, bool black) {
+  const float t = fminf(fmaxf(__fmul_rn(255.0f, v), 0.f), 255.f);
+  return black ? 0u : (unsigned)t;
+}
+
+// the 12 bytes of 4 pixels' (r, g, b) as three little-endian words
+__device__ __forceinline__ void store_rgb4(unsigned char* dst, const f32x4 (&c)[3], const f32x4& mask) {
+  unsigned q[12];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) q[j * 3 + ch] = u8_of(c[ch][j], mask[j] != 0.f);
+  unsigned* o = reinterpret_cast<unsigned*>(dst);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) o[k] = q[4 * k] | (q[4 * k + 1] << 8) | (q[4 * k + 2] << 16) | (q[4 * k + 3] << 24);
+}
+
+// Everything behind the decoder in one rollout step of predict_video (trainer.py:1317-1318, 1351-1355, 1398-1407): the
+// composite (composite_fwd_kernel's expression, term for term: the frame fed back is bit-identical), and both frames
+// blacked with the true mask, scaled, cast and laid out (H, W, 3) in the uint8 video buffers.  A thread owns 4
+// consecutive pixels of one image row (W % 4 == 0): float4 loads of the 3 prev planes, the 3 target planes, the mask
+// and 4 x4 pixels (64 contiguous bytes); three float4 stores to pred, 12 contiguous bytes to each uint8 frame.  Image b
+// scores against target / mask b % nt (S sample groups over the same nt videos); the true frame is written once.
+__global__ void predict_frames_kernel(const f32x4* x4, const float* prev, const float* target, const float* true_mask,
+                                      float* pred, unsigned char* gen_u8, unsigned char* true_u8, long image_stride,
+                                      int n, int nt, int HW) {
+  const int QW = HW >> 2;  // pixel quads per image
+  const long nq = (long)n * QW;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nq; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / QW;
+    const int p = (int)(i - b * QW) << 2;
+    const long bt = b % nt;
+    f32x4 out[3];
+    if (x4) {
+      f32x4 v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = x4[b * HW + p + j];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const long o = (b * 3 + c) * HW + p;
+        const f32x4 pv = *reinterpret_cast<const f32x4*>(prev + o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float m = v[j].w;
+          out[c][j] = (1.f - m) * pv[j] + m * v[j][c];
+        }
+        *reinterpret_cast<f32x4*>(pred + o) = out[c];
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) out[c] = *reinterpret_cast<const f32x4*>(pred + (b * 3 + c) * HW + p);
+    }
+    const f32x4 mk = *reinterpret_cast<const f32x4*>(true_mask + bt * HW + p);
+    store_rgb4(gen_u8 + b * image_stride + (long)p * 3, out, mk);
+    if (true_u8 && b < nt) {
+      f32x4 tg[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) tg[c] = *reinterpret_cast<const f32x4*>(target + (bt * 3 + c) * HW + p);
+      store_rgb4(true_u8 + b * image_stride + (long)p * 3, tg, mk);
+    }
+  }
+}
+
 // ---- reconstruction losses --------------------------------------------------
 // per_sample[b][0..7]: 0 main sum, 1 #world values (3 per unmasked pixel), 2 sum robot d^2, 3 #robot values,
 //                      4 sum world d^2
@@ -688,6 +755,24 @@ int rac_composite_bwd(const float* dout, const float* x4, const float* prev, flo
   hipLaunchKernelGGL(composite_bwd_kernel, dim3(grid_for((long)B * HW)), dim3(256), 0, ST(stream), dout,
                      (const f32x4*)x4, prev, (f32x4*)dx4, dprev, B, HW);
   return check_launch("rac_composite_bwd");
+}
+
+int rac_predict_frames(const float* x4, const float* prev, const float* target, const float* true_mask, float* pred,
+                       uint8_t* gen_u8, uint8_t* true_u8, int64_t image_stride, int32_t n, int32_t nt, int32_t H,
+                       int32_t W, void* stream) {
+  RAC_REQUIRE(true_mask && pred && gen_u8 && n > 0 && nt > 0 && H > 0 && W > 0 && (x4 == nullptr || prev) &&
+                  (true_u8 == nullptr || target),
+              "rac_predict_frames: bad args");
+  RAC_REQUIRE(W % 4 == 0 && n % nt == 0 && image_stride >= (int64_t)H * W * 3 && image_stride % 4 == 0,
+              "rac_predict_frames: W % 4 == 0, n a multiple of nt, image_stride >= H*W*3 and a multiple of 4");
+  RAC_REQUIRE(aligned16(pred) && aligned16(true_mask) && (!x4 || (aligned16(x4) && aligned16(prev))) &&
+                  (!true_u8 || (aligned16(target) && (reinterpret_cast<uintptr_t>(true_u8) & 3) == 0)) &&
+                  (reinterpret_cast<uintptr_t>(gen_u8) & 3) == 0 && (long)H * W < (1L << 29),
+              "rac_predict_frames: 16-byte aligned float buffers, 4-byte aligned uint8 frames");
+  const int HW = H * W;
+  hipLaunchKernelGGL(predict_frames_kernel, dim3(grid_for((long)n * (HW / 4))), dim3(256), 0, ST(stream),
+                     (const f32x4*)x4, prev, target, true_mask, pred, gen_u8, true_u8, (long)image_stride, n, nt, HW);
+  return check_launch("rac_predict_frames");
 }
 
 int rac_recon_loss_fwd(int32_t kind, const float* pred, const float* target, const float* mask, float robot_weight,

@@ -3148,6 +3148,38 @@ def copy_baseline(image: torch.Tensor, next_image: torch.Tensor, next_mask: torc
     return out
 
 
+def predict_frames(x4, prev, target, true_mask, gen_u8, true_u8, step: int, pred=None) -> torch.Tensor:
+    """One rollout step's tail of `_predict_video` (trainer.py:1317-1318, 1351-1355, 1398-1407) in one launch: the
+    composite of the decoder's (n, H, W, 4) map `x4` over `prev` (returned, the bits of `Composite`), and step `step`
+    of the uint8 videos `gen_u8` (n, T, H, W, 3) and `true_u8` (nt, T, H, W, 3; None: not written), both blacked with
+    `true_mask` (nt, 1, H, W).  n is a multiple of nt: image b is scored against video b % nt.
+    `x4=None`: `pred` is the finished frame (--model copy) and only the uint8 frames are written."""
+    _require_cuda(true_mask)
+    nt, _, H, W = true_mask.shape
+    n, T = gen_u8.shape[0], gen_u8.shape[1]
+    f32 = torch.float32
+    ok = (gen_u8.dtype == torch.uint8 and gen_u8.is_contiguous() and tuple(gen_u8.shape[2:]) == (H, W, 3)
+          and 0 <= step < T and n % nt == 0 and tuple(target.shape) == (nt, 3, H, W)
+          and (true_u8 is None or (true_u8.dtype == torch.uint8 and true_u8.is_contiguous()
+                                   and tuple(true_u8.shape) == (nt, T, H, W, 3))))
+    if x4 is not None:
+        ok = ok and tuple(x4.shape) == (n, H, W, 4) and tuple(prev.shape) == (n, 3, H, W) and x4.is_contiguous()
+        prev = prev.detach().to(f32).contiguous()
+        pred = torch.empty((n, 3, H, W), device=x4.device, dtype=f32)
+    else:
+        ok = ok and pred is not None and tuple(pred.shape) == (n, 3, H, W) and pred.dtype == f32 and pred.is_contiguous()
+    if not ok:
+        raise _lib.RacError(f"predict_frames: shapes do not fit (mask {tuple(true_mask.shape)}, frames "
+                            f"{tuple(gen_u8.shape)}, step {step})")
+    target = target.detach().to(f32).contiguous()
+    true_mask = true_mask.detach().to(f32).contiguous()
+    off = step * H * W * 3
+    call("rac_predict_frames", ptr(x4), ptr(prev) if x4 is not None else None, ptr(target), ptr(true_mask), ptr(pred),
+         gen_u8.data_ptr() + off, None if true_u8 is None else true_u8.data_ptr() + off, T * H * W * 3, n, nt, H, W,
+         stream_ptr())
+    return pred
+
+
 class ZeroRegion(torch.autograd.Function):
     """zero_robot_region (src/utils/image.py:5-19), out of place."""
 

@@ -551,6 +551,205 @@ class PredictionTrainer(object):
             losses[name] = v
         return losses
 
+    # ------------------------------------------------------------ video export
+    def predict_video(self, data):
+        """Generate the predicted and the ground-truth videos of a batch for an FVD computation (trainer.py:1149-1224):
+        windows of n_eval frames, each rolled out autoregressively on the prior (`_predict_video`).  Returns the scalar
+        metrics averaged over the windows plus `gen_imgs` / `true_imgs`: lists with one uint8 (B, n_eval-1, H, W, 3)
+        array per window, the robot region blacked with the true mask.  `--model svg` under a `finetune*` experiment
+        draws three prior samples per window and returns the sample whose summed `autoreg_world_loss` is smallest (a
+        stable sort: ties keep the earlier sample); its index is left in `self.last_best_sample`.
+
+        The three samples of a window run as ONE batch of 3 B videos (`RAC_PREDICT_BATCH_SAMPLES=0`: one after the
+        other, as the reference does).  The frozen path's arithmetic does not depend on what shares a video's batch, so
+        both orders give the same frames; `model.eps_source` is asked for (3 B, z, h, w) per draw, sample s in rows
+        [s B, (s+1) B).  Without an `eps_source` one `torch.randn` of that shape is drawn: the same distribution, but
+        not the random stream three sequential passes would consume.
+
+        finetune_* windows take their states and masks from `trainer.robot_model` under the condition `_eval_video`
+        uses (the model takes masks or robot states).  The reference calls the robot model unconditionally under
+        `finetune*`; the two differ only where the reference itself fails (a model without either input has no use for
+        `pred_masks`, and `out` stays unbound for experiments other than finetune_locobot without a learned model)."""
+        cf = self._config
+        num_samples = 3 if (cf.model == "svg" and "finetune" in cf.experiment) else 1
+        finetune = "finetune" in cf.experiment and (cf.model_use_mask or cf.model_use_robot_state)
+        if finetune and getattr(self, "robot_model", None) is None:
+            raise NotImplementedError(
+                "finetune_* evaluation rolls out on the robot model's states and masks (trainer.py:520-543): set "
+                "`trainer.robot_model` (the reference's LocobotAnalyticalModel, or robot_atlas.AtlasRobotModel)")
+        batched = num_samples > 1 and os.environ.get("RAC_PREDICT_BATCH_SAMPLES", "1") == "1"
+        x = data["images"]
+        T = len(x)
+        window = cf.n_eval
+        sampled = [defaultdict(float) for _ in range(num_samples)]
+        for i in range(floor(T / window)):
+            s, e = i * window, (i + 1) * window
+            batch = {"images": x[s:e], "states": data["states"][s:e], "actions": data["actions"][s:e - 1],
+                     "masks": data["masks"][s:e], "pred_masks": data["masks"][s:e], "robot": data["robot"]}
+            if "qpos" in data:
+                batch["qpos"] = data["qpos"][s:e]
+            if "folder" in data:
+                batch["folder"] = data["folder"]
+            if getattr(cf, "model_use_heatmap", False):
+                batch["heatmaps"] = data["heatmaps"][s:e]
+            if finetune:
+                # predicted states / masks drive the rollout, the true masks score and black the frames (trainer.py:1180-1202)
+                if getattr(cf, "preprocess_action", "raw") != "raw":
+                    batch["raw_actions"], batch["raw_states"] = data["raw_actions"][s:e - 1], data["raw_states"][s:e]
+                    batch["raw_low"], batch["raw_high"] = data["raw_low"], data["raw_high"]
+                batch["low"], batch["high"] = data["low"], data["high"]
+                out = self.robot_model.predict_batch(batch)
+                if getattr(cf, "model_use_heatmap", False):
+                    batch["states"], batch["pred_masks"], batch["heatmaps"] = out
+                else:
+                    batch["states"], batch["pred_masks"] = out
+            if batched:
+                outs = self._predict_video(batch, num_samples=num_samples)
+            else:
+                outs = [self._predict_video(batch) for _ in range(num_samples)]
+            for sample, losses in zip(sampled, outs):
+                for k, v in losses.items():
+                    if k in ("true_imgs", "gen_imgs"):
+                        if k not in sample:
+                            sample[k] = []
+                        sample[k].append(v)
+                    else:
+                        sample[k] += v
+        order = list(range(num_samples))
+        if cf.model == "svg":  # the best sample by world error (trainer.py:1216-1218; list.sort is stable)
+            order.sort(key=lambda n: sampled[n]["autoreg_world_loss"])
+        self.last_best_sample = order[0]
+        best = sampled[order[0]]
+        for k in best:
+            if k not in ("true_imgs", "gen_imgs"):
+                best[k] /= floor(T / window)
+        return best
+
+    @torch.no_grad()
+    def _predict_video(self, data, autoregressive=True, num_samples=1):
+        """Roll one n_eval snippet out on the prior and return its metrics and its frames (trainer.py:1227-1408): the
+        loss keys of `_eval_step`, averaged over the n_eval - 1 predicted frames, the k-step keys as the reference's
+        `_predict_video` defines them (which is not how `_eval_step` does), and `gen_imgs` / `true_imgs`, uint8
+        (B, n_eval-1, H, W, 3), robot region blacked with the true mask.
+
+        Per step ONE launch (`ops.predict_frames`) composites the decoder's output and writes both uint8 frames into the
+        device-side video buffer; the call ends in one device->host copy of that buffer and one of the stacked scalars.
+
+        `num_samples` = S > 1 rolls S prior samples of the snippet as one batch of S B videos (inputs repeated per
+        sample group, metrics per group on contiguous slices, the true frames written once) and returns a list of S
+        dicts that share one `true_imgs` array."""
+        from .metrics import masked_psnr_ssim
+        cf = self._config
+        dev, f32 = self._device, torch.float32
+        S = int(num_samples)
+        x = data["images"].to(dev, f32)
+        states = data["states"].to(dev, f32)
+        ac = data["actions"].to(dev, f32)
+        true_masks = data["masks"].to(dev, f32)
+        masks = data["pred_masks"].to(dev, f32)
+        svg = cf.model == "svg"
+        if S > 1 and not svg:
+            raise ValueError("only --model svg draws samples")
+        heatmaps = data["heatmaps"].to(dev, f32) if getattr(cf, "model_use_heatmap", False) and svg else None
+        robot_name = np.array(data["robot"])
+        all_robots = sorted(set(robot_name))
+        bs = min(cf.test_batch_size, x.shape[1])
+        self.model.init_hidden(S * bs)
+        if S > 1:  # sample group s = rows [s bs, (s+1) bs)
+            rep = lambda t: t.repeat((1, S) + (1,) * (t.dim() - 2))
+            states, ac, masks = rep(states), rep(ac), rep(masks)
+            heatmaps = rep(heatmaps) if heatmaps is not None else None
+        frame_in = lambda i: x[i] if S == 1 else x[i].repeat(S, 1, 1, 1)
+        n_steps = cf.n_eval - 1
+        H, W = x.shape[-2], x.shape[-1]
+        # gen frames of the S groups, then the true frames: one buffer, one copy to the host
+        frames = torch.empty(((S + 1) * bs, n_steps, H, W, 3), device=dev, dtype=torch.uint8)
+        gen_u8, true_u8 = frames[:S * bs], frames[S * bs:]
+        prefix = "autoreg" if autoregressive else "1step"
+        dontcare = "dontcare" in cf.reconstruction_loss or cf.black_robot_input
+        log, klog = [], []  # (sample, name, scalar tensor); (sample, step, psnr, ssim, world_mse)
+        x_pred = skip = None
+        for i in range(1, cf.n_eval):
+            x_j = x_pred if (autoregressive and i > 1) else frame_in(i - 1)
+            m_j, r_j, a_j = masks[i - 1], states[i - 1], ac[i - 1]
+            m_i, r_i = masks[i], states[i]
+            x_i, tm = x[i].contiguous(), true_masks[i].contiguous()
+            if cf.last_frame_skip:
+                skip = None
+            m_in = torch.cat([m_j, m_i], 1) if cf.model_use_future_mask else m_j
+            r_in = (r_j, r_i) if cf.model_use_future_robot_state else r_j
+            hm_in = None
+            if heatmaps is not None:
+                hm_in = torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap else heatmaps[i - 1]
+            if cf.model == "copy":
+                x_pred = self.model(x_j, m_j, x_i, m_i)  # on the rollout's masks (`pred_masks`)
+                ops.predict_frames(None, None, x_i, tm, gen_u8, true_u8, i - 1, pred=x_pred)
+            else:
+                if svg:
+                    x4, curr_skip, mu, logvar, mu_p, logvar_p = self.model.forward_maps(
+                        x_j, m_in, r_in, hm_in, a_j, True, r_i, skip, force_use_prior=True,
+                        zero_mask=m_j if dontcare else None)
+                else:
+                    x4, curr_skip = self.model.forward_maps(x_j, m_in, r_j, a_j, skip, zero_mask=m_j if dontcare else None)
+                x_pred = ops.predict_frames(x4, x_j, x_i, tm, gen_u8, true_u8, i - 1)
+                if i <= cf.n_past:
+                    skip = curr_skip
+            for n in range(S):
+                xp = x_pred[n * bs:(n + 1) * bs]
+                rec = self._recon_loss(xp, x_i, tm)
+                log += [(n, f"{prefix}_recon_loss", rec[0]), (n, f"{prefix}_robot_loss", rec[1]),
+                        (n, f"{prefix}_world_loss", rec[2])]
+                p, s = masked_psnr_ssim(xp, x_i, tm)  # robot region blacked with the true mask
+                p = p.mean()
+                log += [(n, f"{prefix}_psnr", p), (n, f"{prefix}_ssim", s)]
+                if autoregressive:
+                    klog.append((n, i, p, s, rec[2]))
+                if len(all_robots) > 1:
+                    for r in all_robots:
+                        idx = torch.from_numpy(np.nonzero(robot_name == r)[0]).to(dev)
+                        sub = ops.ReconLoss.apply(xp[idx].contiguous(), x_i[idx].contiguous(), tm[idx].contiguous(),
+                                                  None, 0, 0.0)
+                        log += [(n, f"{prefix}_{r}_robot_loss", sub[1]), (n, f"{prefix}_{r}_world_loss", sub[2])]
+                if svg:
+                    sl = slice(n * bs, (n + 1) * bs)
+                    kl = ops.KLLoss.apply(mu[sl], logvar[sl], mu_p[sl], logvar_p[sl], bs)
+                    log.append((n, f"{prefix}_kld", kl[0]))
+        scalars = [t for _, _, t in log] + [t for e in klog for t in e[2:]]
+        vals = torch.stack([t.reshape(()) for t in scalars]).cpu().tolist()
+        host = frames.cpu().numpy()
+        outs = self._video_scalars([(n, name) for n, name, _ in log], vals[:len(log)], [(n, i) for n, i, *_ in klog],
+                                   vals[len(log):], n_steps, S)
+        for n, losses in enumerate(outs):
+            losses["gen_imgs"] = host[n * bs:(n + 1) * bs]
+            losses["true_imgs"] = host[S * bs:]
+        return outs[0] if S == 1 else outs
+
+    @staticmethod
+    def _video_scalars(log, vals, klog, kvals, n_steps, num_samples=1):
+        """The host half of `_predict_video`'s metrics (trainer.py:1386-1393): `log[j]` = (sample, key) of the per-step
+        scalar `vals[j]`, `klog[j]` = (sample, step i) of the (psnr, ssim, world_mse) triple `kvals[3j:3j+3]`.
+        Returns one loss dict per sample."""
+        outs = [defaultdict(float) for _ in range(num_samples)]
+        for (n, name), v in zip(log, vals):
+            outs[n][name] += v
+        for losses in outs:
+            for k in losses:
+                losses[k] = losses[k] / n_steps  # don't count the first step
+        # k-step keys (trainer.py:1362-1367): step i's values are added to every k in [i, n_eval - 1)
+        k_losses = [defaultdict(float) for _ in range(num_samples)]
+        for j, (n, i) in enumerate(klog):
+            p, s, w = kvals[3 * j:3 * j + 3]
+            for k in range(i, n_steps):
+                k_losses[n][f"{k}_step_psnr"] += p
+                k_losses[n][f"{k}_step_ssim"] += s
+                k_losses[n][f"{k}_step_world_loss"] += w
+        for n, losses in enumerate(outs):
+            for key, v in k_losses[n].items():
+                # the reference divides by the key's FIRST CHARACTER (trainer.py:1391), kept verbatim: that is k only
+                # for k <= 9 ("12_step_psnr" is divided by 1)
+                losses[key] = v / float(key[0])
+        return outs
+
     # ------------------------------------------------------------------- plots
     @torch.no_grad()
     def plot(self, data, epoch, name, random_start=True, instance=None):
