@@ -1896,6 +1896,23 @@ class Upsample2(torch.autograd.Function):
         return dx
 
 
+def _tilecat(vs, m0, m1, pad: int, per_image: bool = False, like=None) -> torch.Tensor:
+    """[tile(v) for v in vs (at most three; None entries are skipped) | m0 | m1 | `pad` zero channels] along channels, tagged
+    with its amax slot (one per image when `per_image`).  `like`: a map of the output's (B, H, W) where m0 is None."""
+    like = m0 if m0 is not None else like
+    B, H, W, _ = like.shape
+    vs = [v for v in vs if v is not None]
+    vs += [None] * (3 - len(vs))
+    ns = [v.shape[1] if v is not None else 0 for v in vs]
+    c0 = m0.shape[3] if m0 is not None else 0
+    c1 = m1.shape[3] if m1 is not None else 0
+    out = torch.empty((B, H, W, sum(ns) + c0 + c1 + pad), device=like.device, dtype=torch.float32)
+    slot = amax_slot(like.device, B if per_image else 1)
+    call("rac_tilecat_fwd", ptr(vs[0]), ns[0], ptr(vs[1]), ns[1], ptr(vs[2]), ns[2], ptr(m0), c0, ptr(m1), c1, pad,
+         ptr(out), B, H * W, ptr(slot), 1 if per_image else 0, stream_ptr())
+    return tag_amax(out, slot)
+
+
 class TileCat(torch.autograd.Function):
     """[tile(v0) | tile(v1) | tile(v2) | m0 | m1 | 0-pad to a multiple of 4] along channels
     (dynamics.py:591-607,634-640).  Gradients flow to the maps only (actions / robot states are data)."""
@@ -1903,24 +1920,17 @@ class TileCat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v0, v1, v2, m0, m1, frozen=False):
         B, H, W, c0 = m0.shape
-        vs = [v for v in (v0, v1, v2) if v is not None]
-        vs += [None] * (3 - len(vs))
-        ns = [v.shape[1] if v is not None else 0 for v in vs]
+        nv = sum(v.shape[1] for v in (v0, v1, v2) if v is not None)
         c1 = m1.shape[3] if m1 is not None else 0
-        ct = sum(ns) + c0 + c1
+        ct = nv + c0 + c1
         pad = pad4(ct)
         # whole 32-channel chunks where the consumer conv can then run split-precision: maps that fit a tile, and (round 4)
         # the larger maps of the rows kernels too -- the 16x16 latents of a 128x128 model ran their three input convs on
         # the exact-fp32 pipe (21 ms of a 106 ms cfg5 step: rac_conv2d fwd / dgrad / wgrad at 157 TFLOP/s peak)
         if SPLIT_GEMM and ct >= 128 and c0 % 32 == 0 and split_supported(H, W, 3, ct + (-ct) % 32, 128, 0):
             pad = (-ct) % 32
-        out = torch.empty((B, H, W, ct + pad), device=m0.device, dtype=torch.float32)
-        slot = amax_slot(m0.device, B if frozen else 1)
-        call("rac_tilecat_fwd", ptr(vs[0]), ns[0], ptr(vs[1]), ns[1], ptr(vs[2]), ns[2], ptr(m0), c0, ptr(m1), c1, pad,
-             ptr(out), B, H * W, ptr(slot), 1 if frozen else 0, stream_ptr())
-        tag_amax(out, slot)
-        ctx.meta = (sum(ns), c0, c1)
-        return out
+        ctx.meta = (nv, c0, c1)
+        return _tilecat((v0, v1, v2), m0, m1, pad, per_image=frozen)
 
     @staticmethod
     def backward(ctx, dout):
@@ -1952,18 +1962,11 @@ def embed_frozen(vs, h, z, weight, bias) -> torch.Tensor:
     """Conv(cat[tile(v0), tile(v1), tile(v2), h, z]) + bias (dynamics.py:591-607,634-640) for the frozen model without
     the concatenated tensor: the conv's first source is h itself, the second a small [tile(v) | z | 0-pad] map, against a
     cached copy of the weight whose input channels are reordered to [h | v | z | 0]."""
-    B, H, W, g = h.shape
-    vs = [v for v in vs if v is not None]
-    nv = sum(v.shape[1] for v in vs)
+    g = h.shape[3]
+    nv = sum(v.shape[1] for v in vs if v is not None)
     cz = z.shape[3] if z is not None else 0
     pad = (-(nv + cz)) % 32
-    vs3 = vs + [None] * (3 - len(vs))
-    small = torch.empty((B, H, W, nv + cz + pad), device=h.device, dtype=torch.float32)
-    slot = amax_slot(h.device, B)
-    call("rac_tilecat_fwd", ptr(vs3[0]), vs3[0].shape[1] if vs3[0] is not None else 0, ptr(vs3[1]),
-         vs3[1].shape[1] if vs3[1] is not None else 0, ptr(vs3[2]), vs3[2].shape[1] if vs3[2] is not None else 0,
-         None, 0, ptr(z), cz, pad, ptr(small), B, H * W, ptr(slot), 1, stream_ptr())
-    tag_amax(small, slot)
+    small = _tilecat(vs, None, z, pad, per_image=True, like=h)
 
     def build():
         w = weight.detach()
@@ -2089,12 +2092,89 @@ def conv_dgrad_slabs(dy, weight, cin: int):
     return slabs, split
 
 
-def recurrent_core_ok(h_all, g: int, z: int, nv: int, cells, head, frame_conv) -> bool:
-    """Configurations the hand-scheduled core takes: plain ConvLSTM cells whose gate convs, the merged posterior head and
-    the frame predictor's 32-channel-padded input conv all run on the split-precision pipe (g >= 128 at 64x64 / 128x128);
-    anything else keeps the autograd path."""
-    if not (RECURRENT_CORE and SPLIT_GEMM and h_all.is_cuda and torch.is_grad_enabled()):
-        return False
+def _step_rows(slabs, n: int, cin: int, T: int, M: int, t: int, col: int = 0):
+    """Rows of step t of batched slabs [n][T M][cin] as a gradient source (the first slab's rows of that step: the other
+    slabs follow at the slab stride)."""
+    rows = slabs.view(n, T, M, cin)[0, t]
+    return (rows, n, slabs.numel() // n if n > 1 else 0, cin, col)
+
+
+# The stage between the ConvLSTM chains of both cores, over any number of images (one step's B, or a window's T*B):
+#   forward   posterior top layer -> merged mu | logvar head -> reparameterisation -> cat[tile(v) | h | z | 0-pad] ->
+#             the frame predictor's padded input conv
+#   backward  that conv's data-gradient slabs, weight and bias gradient and d h -> reparameterisation + KL gradients ->
+#             the head's data-gradient slabs, weight and bias gradient
+# RecurrentCore calls it per step and (CORE_BATCH_THIN) once over the window, NormRecurrentCore once over the window.
+def _draw_eps(plan, mu_steps):
+    """The noise of every step in the reference's order (the prior's draw, dropped, before the posterior's)."""
+    eps = []
+    for mu_t in mu_steps:
+        if plan["draw_prior_noise"]:
+            plan["eps_fn"](mu_t)
+        eps.append(plan["eps_fn"](mu_t))
+    return eps
+
+
+def _refresh_parts(weights, transposed: bool = False) -> None:
+    """Operand parts of every weight of a core (one launch over ALL that changed), on the caller's stream."""
+    for w in weights:
+        weight_parts(w, transposed=transposed)
+
+
+def _posterior_sample(h_post, head, eps, mu_out, lv_out):
+    """mu | logvar = the merged head over `h_post` (written into `mu_out` / `lv_out`), z = eps * exp(logvar / 2) + mu.
+    `eps`: the images' noise, or the list of a window's per-step draws (stacked here, behind the head).  Returns (z, eps)."""
+    sp = stream_ptr()
+    zc = mu_out.shape[-1]
+    slabs, split, stride = conv_forward_split(h_post, None, head[0], want_slabs=True)
+    call("rac_slab_reduce2", ptr(slabs), split, stride, ptr(head[1]), ptr(mu_out), ptr(lv_out), mu_out.numel() // zc, 2 * zc,
+         zc, None, None, sp)
+    if isinstance(eps, list):
+        eps = torch.stack(eps)
+    z = torch.empty_like(mu_out)
+    call("rac_reparam_fwd", ptr(mu_out), ptr(lv_out), ptr(eps), ptr(z), z.numel(), sp)
+    return z, eps
+
+
+def _frame_input(vs, h, z, fw_pad, bias):
+    """(cat, xf): cat[tile(v) | h | z | 0-pad to whole 32-channel chunks] and the frame predictor's input conv over it.
+    `fw_pad()` gives the padded weight (asked for behind the concatenation: it may have to wait for its parameter)."""
+    ct = sum(v.shape[1] for v in vs) + h.shape[3] + z.shape[3]
+    cat = _tilecat(vs, h, z, (-ct) % 32)
+    return cat, conv_forward_split(cat, None, fw_pad(), bias)
+
+
+def _frame_input_bwd(dy_f, cat, fw_pad, fconv, d_h_out, nv: int):
+    """Backward of _frame_input for the (tagged) output gradient `dy_f`: the raw data-gradient slabs (dcat, n_c) over the
+    padded input channels, the deferred weight gradient (un-padded into weight.grad), the bias gradient, and the h window
+    of the slabs summed into `d_h_out`."""
+    cpad, g = fw_pad.shape[1], dy_f.shape[3]
+    dcat, n_c = conv_dgrad_slabs(dy_f, fw_pad, cpad)
+    conv_wgrad_split_acc(dy_f, cat, None, fconv.weight, defer=True)
+    bias_grad_acc(dy_f, fconv.bias)
+    grad_sum([_src(dcat, n_c, cpad, nv)], d_h_out, g)
+    return dcat, n_c
+
+
+def _posterior_head_bwd(dz_src, lv, eps, d_mu, d_lv, h_post, head):
+    """Backward of _posterior_sample: `dz_src` (the z window of the frame predictor's input gradient) and the KL
+    gradients `d_mu` / `d_lv` (or None) -> the head's output gradient -> its raw data-gradient slabs (dhead, n_h), its
+    deferred weight gradient and its bias gradient."""
+    zc, g = lv.shape[-1], h_post.shape[3]
+    dy_h = torch.empty(tuple(h_post.shape[:3]) + (2 * zc,), device=lv.device, dtype=torch.float32)
+    slot = amax_slot(lv.device)
+    call("rac_reparam_head_bwd", _pack_srcs([dz_src]), 1, ptr(lv), ptr(eps), ptr(d_mu), ptr(d_lv), ptr(dy_h),
+         lv.numel() // zc, zc, ptr(slot), stream_ptr())
+    tag_amax(dy_h, slot)
+    dhead, n_h = conv_dgrad_slabs(dy_h, head[0], g)
+    conv_wgrad_split_acc(dy_h, h_post, None, head[0], defer=True)
+    bias_grad_acc(dy_h, head[1])
+    return dhead, n_h
+
+
+def _core_geometry_ok(h_all, g: int, z: int, nv: int, head, frame_conv) -> bool:
+    """What both cores need of the shapes: the merged posterior head and the frame predictor's 32-channel-padded input
+    conv run on the split-precision pipe."""
     _, H, W, gg = h_all.shape
     if gg != g or g % 32 or z % 4 or head is None or not gauss_head_ok((1, H, W, g), head[0]):
         return False
@@ -2102,8 +2182,18 @@ def recurrent_core_ok(h_all, g: int, z: int, nv: int, cells, head, frame_conv) -
     cpad = ct + (-ct) % 32
     if not (ct >= 128 and split_supported(H, W, 3, cpad, 128, 0)):  # TileCat's whole-chunk padding rule
         return False
-    if not split_supported(H, W, frame_conv.weight.shape[2], cpad, frame_conv.weight.shape[0], 0):
+    return split_supported(H, W, frame_conv.weight.shape[2], cpad, frame_conv.weight.shape[0], 0)
+
+
+def recurrent_core_ok(h_all, g: int, z: int, nv: int, cells, head, frame_conv) -> bool:
+    """Configurations the hand-scheduled core takes: plain ConvLSTM cells whose gate convs, the merged posterior head and
+    the frame predictor's 32-channel-padded input conv all run on the split-precision pipe (g >= 128 at 64x64 / 128x128);
+    anything else keeps the autograd path."""
+    if not (RECURRENT_CORE and SPLIT_GEMM and h_all.is_cuda and torch.is_grad_enabled()):
         return False
+    if not _core_geometry_ok(h_all, g, z, nv, head, frame_conv):
+        return False
+    _, H, W, _ = h_all.shape
     for cell in cells:
         w = cell.gates.weight
         if tuple(w.shape[:2]) != (4 * g, 2 * g) or not split_supported(H, W, w.shape[2], 2 * g, 4 * g, g):
@@ -2202,8 +2292,7 @@ class RecurrentCore(torch.autograd.Function):
         hp_s, hq_s, mu_s, lv_s = step(h_pred_all), step(h_prior_all), step(mu_all), step(lv_all)
         state = {L: list(plan["init_state"][L]) for L in ("prior", "post", "fp")}
         cells = plan["cells"]  # {L: (cell0, cell1)}
-        head_w, head_b = plan["head"]
-        fconv = plan["frame_conv"]
+        head, fconv = plan["head"], plan["frame_conv"]
 
         def run_cell(L, l, x, h_out=None):
             cell = cells[L][l].gates
@@ -2219,9 +2308,7 @@ class RecurrentCore(torch.autograd.Function):
             return h, {"x": x, "h_prev": h_prev, "c_prev": c_prev, "act": act, "c": c}
 
         vs = plan["vs"]  # per step: the tiled vectors (action, robot state(s)) of the frame predictor's input conv
-        nv = plan["nv"]
-        ct = nv + g + z
-        pad = (-ct) % 32
+        ct = plan["nv"] + g + z
         staged = CORE_LAYER_MAJOR and not (CHAIN_STREAMS and h_all.is_cuda)  # (chains in order: their weights may arrive in order)
         if not staged:
             param_wait()
@@ -2230,22 +2317,13 @@ class RecurrentCore(torch.autograd.Function):
         def fw_pad_now():  # the frame predictor's padded input-conv weight: rebuilt from the parameter, so behind its update
             if not fw_box:
                 param_wait(fconv.weight)
-                fw_box.append(padded_weight(fconv.weight, ct + pad))
+                fw_box.append(padded_weight(fconv.weight, ct + (-ct) % 32))
                 weight_parts(fw_box[0])
             return fw_box[0]
         if not staged:
             fw_pad_now()
-        # the noise of every step, drawn in the reference's order (the prior's draw, dropped, before the posterior's)
-        eps_all = []
-        for t in range(T):
-            if plan["draw_prior_noise"]:
-                plan["eps_fn"](mu_s[t])
-            eps_all.append(plan["eps_fn"](mu_s[t]))
-        # (operand parts of every weight of the core are refreshed -- one launch over ALL weights -- on the caller's stream)
-        for L in ("prior", "post", "fp"):
-            for cell in cells[L]:
-                weight_parts(cell.gates.weight)
-        weight_parts(head_w)
+        eps_all = _draw_eps(plan, mu_s)
+        _refresh_parts([c.gates.weight for L in ("prior", "post", "fp") for c in cells[L]] + [head[0]])
         region = _ChainRegion(dev, True)
         tape = [dict() for _ in range(T)]
         h0 = {L: [None] * T for L in ("prior", "post", "fp")}
@@ -2263,27 +2341,12 @@ class RecurrentCore(torch.autograd.Function):
             h0["post"][t], tape[t]["post0"] = run_cell("post", 0, retag(post_steps[t], amax_tag(post_all)))
 
         def post_l1(t):
-            sp = stream_ptr()
             h_post, tape[t]["post1"] = run_cell("post", 1, h0["post"][t])
-            slabs, split, stride = conv_forward_split(h_post, None, head_w, want_slabs=True)
-            call("rac_slab_reduce2", ptr(slabs), split, stride, ptr(head_b), ptr(mu_s[t]), ptr(lv_s[t]), M, 2 * z, z,
-                 None, None, sp)
-            z_t = torch.empty_like(mu_s[t])
-            call("rac_reparam_fwd", ptr(mu_s[t]), ptr(lv_s[t]), ptr(eps_all[t]), ptr(z_t), z_t.numel(), sp)
-            z_all[t] = z_t
+            z_all[t], _ = _posterior_sample(h_post, head, eps_all[t], mu_s[t], lv_s[t])
             tape[t].update(h_post=h_post, eps=eps_all[t])
 
         def fp_in(t):
-            sp = stream_ptr()
-            v3 = list(vs[t]) + [None] * (3 - len(vs[t]))
-            cat = torch.empty((B, H, W, ct + pad), device=dev, dtype=torch.float32)
-            slot = amax_slot(dev)
-            call("rac_tilecat_fwd", ptr(v3[0]), v3[0].shape[1] if v3[0] is not None else 0, ptr(v3[1]),
-                 v3[1].shape[1] if v3[1] is not None else 0, ptr(v3[2]), v3[2].shape[1] if v3[2] is not None else 0,
-                 ptr(h_steps[t]), g, ptr(z_all[t]), z, pad, ptr(cat), B, H * W, ptr(slot), 0, sp)
-            tag_amax(cat, slot)
-            xf_all[t] = conv_forward_split(cat, None, fw_pad_now(), fconv.bias)
-            tape[t]["cat"] = cat
+            tape[t]["cat"], xf_all[t] = _frame_input(vs[t], h_steps[t], z_all[t], fw_pad_now, fconv.bias)
 
         def fp_l0(t):
             h0["fp"][t], tape[t]["fp0"] = run_cell("fp", 0, xf_all[t])
@@ -2304,31 +2367,15 @@ class RecurrentCore(torch.autograd.Function):
         def post_head_all():
             # mu | logvar head and the reparameterisation of ALL steps in one launch each (M = T B H W rows instead of T launches
             # of B H W: five 20 us launches at 0.07 of the pipe become one at ~0.4)
-            sp = stream_ptr()
-            h_all_post = tag_amax(thin["h_post"], one)
-            slabs, split, stride = conv_forward_split(h_all_post, None, head_w, want_slabs=True)
-            call("rac_slab_reduce2", ptr(slabs), split, stride, ptr(head_b), ptr(mu_all), ptr(lv_all), T * M, 2 * z, z,
-                 None, None, sp)
-            eps_stack = torch.stack(eps_all)
-            zs = torch.empty_like(mu_all)
-            call("rac_reparam_fwd", ptr(mu_all), ptr(lv_all), ptr(eps_stack), ptr(zs), zs.numel(), sp)
-            thin.update(eps=eps_stack, z=zs)
+            thin["z"], thin["eps"] = _posterior_sample(tag_amax(thin["h_post"], one), head, eps_all, mu_all, lv_all)
             for t in range(T):
-                tape[t]["eps"] = eps_stack[t]
+                tape[t]["eps"] = thin["eps"][t]
 
         def fp_in_all():
             # cat[tile(v) | h_t | z_t] and the frame predictor's input conv over all steps at once
-            sp = stream_ptr()
-            v3 = [torch.cat([vs[t][k] for t in range(T)]) if k < len(vs[0]) else None for k in range(3)]
-            cat = torch.empty((T * B, H, W, ct + pad), device=dev, dtype=torch.float32)
-            slot = amax_slot(dev)
-            call("rac_tilecat_fwd", ptr(v3[0]), v3[0].shape[1] if v3[0] is not None else 0, ptr(v3[1]),
-                 v3[1].shape[1] if v3[1] is not None else 0, ptr(v3[2]), v3[2].shape[1] if v3[2] is not None else 0,
-                 ptr(h_all), g, ptr(thin["z"]), z, pad, ptr(cat), T * B, H * W, ptr(slot), 0, sp)
-            tag_amax(cat, slot)
-            xf = conv_forward_split(cat, None, fw_pad_now(), fconv.bias)
-            thin.update(cat=cat, xf=xf)
-            xs = step(xf)
+            v_all = [torch.cat([vs[t][k] for t in range(T)]) for k in range(len(vs[0]))]
+            thin["cat"], thin["xf"] = _frame_input(v_all, h_all, thin["z"], fw_pad_now, fconv.bias)
+            xf, xs = thin["xf"], step(thin["xf"])
             for t in range(T):
                 xf_all[t] = retag(xs[t], amax_tag(xf))
 
@@ -2387,8 +2434,7 @@ class RecurrentCore(torch.autograd.Function):
         g, z, nv = plan["g"], plan["z"], plan["nv"]
         M = B * H * W
         dev = ctx.lv_all.device
-        cells, fconv = plan["cells"], plan["frame_conv"]
-        head_w, head_b = plan["head"]
+        cells, fconv, head = plan["cells"], plan["frame_conv"], plan["head"]
         ct = nv + g + z
         cpad = ct + (-ct) % 32
         fw_pad = padded_weight(fconv.weight, cpad)
@@ -2425,11 +2471,7 @@ class RecurrentCore(torch.autograd.Function):
         # stream: the frame predictor's run under the posterior's and the prior's backward, not only under the encoder's.
         chain_ws = lambda L, extra: [c.gates.weight for c in cells[L]] + extra
         dcats = [None] * T
-        for L in ("prior", "post", "fp"):  # (the data gradients' operand parts: refreshed on the caller's stream)
-            for cell in cells[L]:
-                weight_parts(cell.gates.weight, transposed=True)
-        weight_parts(head_w, transposed=True)
-        weight_parts(fw_pad, transposed=True)
+        _refresh_parts(chain_ws("prior", []) + chain_ws("post", []) + chain_ws("fp", [head[0], fw_pad]), transposed=True)
         region = _ChainRegion(dev, True)
         dz_ready = [None] * T
         top = {L: [None] * T for L in ("prior", "post", "fp")}  # the top layer's data-gradient slabs per step
@@ -2439,32 +2481,41 @@ class RecurrentCore(torch.autograd.Function):
             ext = [_src(d_hpred[t], 1, g)] if d_hpred is not None else []
             top["fp"][t] = cell_bwd("fp", 1, tape[t]["fp1"], ext)
 
-        def fp_b0(t):  # ... layer 0, then the input conv over cat[v | h_t | z_t]
+        thin = ctx.thin  # forward ran the posterior head and the frame predictor's input conv over all steps at once
+        if thin is not None:
+            dy_f_all = torch.empty((T * B, H, W, g), device=dev, dtype=torch.float32)
+            slot_f = amax_slot(dev)
+        at = lambda d, t: None if d is None else d[t]
+
+        def fp_b0(t):  # ... layer 0, then (per step) the input conv over cat[v | h_t | z_t]
             s0 = cell_bwd("fp", 0, tape[t]["fp0"], [top["fp"][t]])
+            if thin is not None:  # the gradient of the input conv's output: slice t of one tensor (fp_in_b_all)
+                grad_sum([s0], dy_f_all.view(T, B, H, W, g)[t], g, slot_f)
+                return
             dy_f = torch.empty((B, H, W, g), device=dev, dtype=torch.float32)
             slot = amax_slot(dev)
             tag_amax(grad_sum([s0], dy_f, g, slot), slot)
-            dcat, n_c = conv_dgrad_slabs(dy_f, fw_pad, cpad)
+            dcats[t] = _frame_input_bwd(dy_f, tape[t]["cat"], fw_pad, fconv, d_h_all[t], nv)
             dz_ready[t] = region.event("fp")  # the posterior's step t may start
-            conv_wgrad_split_acc(dy_f, tape[t]["cat"], None, fconv.weight, defer=True)  # un-pads into weight.grad
-            bias_grad_acc(dy_f, fconv.bias)
-            grad_sum([_src(dcat, n_c, cpad, nv)], d_h_all[t], g)
-            dcats[t] = (dcat, n_c)
 
-        def post_b1(t):  # posterior: reparameterisation + KL gradients -> merged head -> layer 1
+        def fp_in_b_all():  # the input conv's data gradient, its weight gradient and d h, over all steps
+            thin["dcat"] = _frame_input_bwd(tag_amax(dy_f_all, slot_f), thin["cat"], fw_pad, fconv, d_h_all, nv)
+
+        def post_head_b_all():  # reparameterisation + KL gradients and the merged head's data gradient, all steps
+            dcat, n_c = thin["dcat"]
+            thin["dhead"] = _posterior_head_bwd(_src(dcat, n_c, cpad, nv + g), ctx.lv_all, thin["eps"], d_mu, d_lv,
+                                                tag_amax(thin["h_post"], amax_one(dev)), head)
+
+        def post_b1(t):  # posterior: reparameterisation + KL gradients -> merged head (per step, or its rows t) -> layer 1
             rec = tape[t]
-            dcat, n_c = dcats[t]
-            dy_h = torch.empty((B, H, W, 2 * z), device=dev, dtype=torch.float32)
-            slot = amax_slot(dev)
-            call("rac_reparam_head_bwd", _pack_srcs([_src(dcat, n_c, cpad, nv + g)]), 1, ptr(lv_s[t]), ptr(rec["eps"]),
-                 ptr(d_mu[t]) if d_mu is not None else None, ptr(d_lv[t]) if d_lv is not None else None, ptr(dy_h), M, z,
-                 ptr(slot), stream_ptr())
-            tag_amax(dy_h, slot)
-            dhead, n_h = conv_dgrad_slabs(dy_h, head_w, g)
-            conv_wgrad_split_acc(dy_h, rec["h_post"], None, head_w, defer=True)
-            bias_grad_acc(dy_h, head_b)
-            dheads[t] = dhead
-            top["post"][t] = cell_bwd("post", 1, rec["post1"], [_src(dhead, n_h, g, 0)])
+            if thin is not None:
+                src = _step_rows(*thin["dhead"], g, T, M, t)
+            else:
+                dcat, n_c = dcats[t]
+                dheads[t], n_h = _posterior_head_bwd(_src(dcat, n_c, cpad, nv + g), lv_s[t], rec["eps"], at(d_mu, t),
+                                                     at(d_lv, t), rec["h_post"], head)
+                src = _src(dheads[t], n_h, g, 0)
+            top["post"][t] = cell_bwd("post", 1, rec["post1"], [src])
 
         def post_b0(t):  # ... layer 0 -> its input conv's output
             grad_sum([cell_bwd("post", 0, tape[t]["post0"], [top["post"][t]])], d_post_all[t], g, slot_post)
@@ -2478,41 +2529,6 @@ class RecurrentCore(torch.autograd.Function):
 
         steps = range(T - 1, -1, -1)
         layer_major = CORE_LAYER_MAJOR and not region.enabled
-        thin = ctx.thin  # forward ran the posterior head and the frame predictor's input conv over all steps at once
-        if thin is not None:
-            dy_f_all = torch.empty((T * B, H, W, g), device=dev, dtype=torch.float32)
-            slot_f = amax_slot(dev)
-
-            def fp_b0(t):  # layer 0 of the frame predictor: the gradient of its input, slice t of one tensor  # noqa: F811
-                s0 = cell_bwd("fp", 0, tape[t]["fp0"], [top["fp"][t]])
-                grad_sum([s0], dy_f_all.view(T, B, H, W, g)[t], g, slot_f)
-
-            def fp_in_b_all():  # the input conv's data gradient, its weight gradient and d h, over all steps
-                tag_amax(dy_f_all, slot_f)
-                dcat, n_c = conv_dgrad_slabs(dy_f_all, fw_pad, cpad)
-                conv_wgrad_split_acc(dy_f_all, thin["cat"], None, fconv.weight, defer=True)
-                bias_grad_acc(dy_f_all, fconv.bias)
-                grad_sum([_src(dcat, n_c, cpad, nv)], d_h_all, g)
-                thin["dcat"] = (dcat, n_c)
-
-            def post_head_b_all():  # reparameterisation + KL gradients and the merged head's data gradient, all steps
-                dcat, n_c = thin["dcat"]
-                dy_h = torch.empty((T * B, H, W, 2 * z), device=dev, dtype=torch.float32)
-                slot = amax_slot(dev)
-                call("rac_reparam_head_bwd", _pack_srcs([_src(dcat, n_c, cpad, nv + g)]), 1, ptr(ctx.lv_all), ptr(thin["eps"]),
-                     ptr(d_mu) if d_mu is not None else None, ptr(d_lv) if d_lv is not None else None, ptr(dy_h), T * M, z,
-                     ptr(slot), stream_ptr())
-                tag_amax(dy_h, slot)
-                dhead, n_h = conv_dgrad_slabs(dy_h, head_w, g)
-                conv_wgrad_split_acc(dy_h, tag_amax(thin["h_post"], amax_one(dev)), None, head_w, defer=True)
-                bias_grad_acc(dy_h, head_b)
-                thin["dhead"] = (dhead, n_h)
-
-            def post_b1(t):  # noqa: F811  (its head gradient: rows t of the batched slabs)
-                dhead, n_h = thin["dhead"]
-                rows = dhead.view(n_h, T, M, g)[0, t]  # (first slab's rows of step t: the others follow at the slab stride)
-                src = (rows, n_h, dhead.numel() // n_h if n_h > 1 else 0, g, 0)
-                top["post"][t] = cell_bwd("post", 1, tape[t]["post1"], [src])
         try:
             if layer_major:  # (see forward: a layer's T data-gradient launches back to back)
                 for piece in (fp_b1, fp_b0):
@@ -2535,7 +2551,7 @@ class RecurrentCore(torch.autograd.Function):
                     for t in steps:
                         region.wait("post", dz_ready[t])
                         post_b1(t), post_b0(t)
-                flush_deferred_wgrads_early(chain_ws("post", [head_w]))  # (ordered behind the posterior's stream)
+                flush_deferred_wgrads_early(chain_ws("post", [head[0]]))  # (ordered behind the posterior's stream)
             with region.on("prior"):
                 if layer_major:
                     for piece in (prior_b1, prior_b0):
@@ -2706,14 +2722,7 @@ NORM_RECURRENT_CORE = os.environ.get("RAC_NORM_RECURRENT_CORE", "1") == "1"
 def norm_recurrent_core_ok(h_all, g: int, z: int, nv: int, cells, head, frame_conv) -> bool:
     if not (NORM_RECURRENT_CORE and RECURRENT_CORE and SPLIT_GEMM and h_all.is_cuda and torch.is_grad_enabled()):
         return False
-    _, H, W, gg = h_all.shape
-    if gg != g or g % 32 or z % 4 or head is None or not gauss_head_ok((1, H, W, g), head[0]):
-        return False
-    ct = nv + g + z
-    cpad = ct + (-ct) % 32
-    if not (ct >= 128 and split_supported(H, W, 3, cpad, 128, 0)):
-        return False
-    if not split_supported(H, W, frame_conv.weight.shape[2], cpad, frame_conv.weight.shape[0], 0):
+    if not _core_geometry_ok(h_all, g, z, nv, head, frame_conv):
         return False
     x_like = h_all[:1]
     for cell in cells:
@@ -2723,6 +2732,11 @@ def norm_recurrent_core_ok(h_all, g: int, z: int, nv: int, cells, head, frame_co
         if not all(p.requires_grad for p in cell.parameters()):
             return False
     return frame_conv.weight.requires_grad and head[0].requires_grad
+
+
+def _norm_chain_ws(cells):
+    """The gate-conv weights of a chain of NormConvLSTMCells: each cell's input half, then its hidden half."""
+    return [w for c in cells for w in (c.ih_gates[0].weight, c.hh_gates[0].weight)]
 
 
 def _plain_map(src, g):
@@ -2740,28 +2754,16 @@ class NormRecurrentCore(torch.autograd.Function):
         T, B, g, z = plan["T"], plan["B"], plan["g"], plan["z"]
         dev = h_all.device
         _, H, W, _ = h_all.shape
-        M = B * H * W
         step = lambda t_: t_.view((T, B) + tuple(t_.shape[1:]))
         one = amax_one(dev)
-        cells = plan["cells"]
-        head_w, head_b = plan["head"]
-        fconv = plan["frame_conv"]
-        nv = plan["nv"]
-        ct = nv + g + z
-        pad = (-ct) % 32
+        cells, head, fconv = plan["cells"], plan["head"], plan["frame_conv"]
+        ct = plan["nv"] + g + z
         param_wait()
-        fw_pad = padded_weight(fconv.weight, ct + pad)
+        fw_pad = padded_weight(fconv.weight, ct + (-ct) % 32)
         mu_all = torch.empty((T * B, H, W, z), device=dev, dtype=torch.float32)
         lv_all = torch.empty_like(mu_all)
-        eps_all = []
-        for t in range(T):  # the noise of every step in the reference's order (the prior's draw, dropped, first)
-            if plan["draw_prior_noise"]:
-                plan["eps_fn"](step(mu_all)[t])
-            eps_all.append(plan["eps_fn"](step(mu_all)[t]))
-        for L in ("prior", "post", "fp"):
-            for cell in cells[L]:
-                weight_parts(cell.ih_gates[0].weight), weight_parts(cell.hh_gates[0].weight)
-        weight_parts(head_w), weight_parts(fw_pad)
+        eps_all = _draw_eps(plan, step(mu_all))
+        _refresh_parts([w for L in ("prior", "post", "fp") for w in _norm_chain_ws(cells[L])] + [head[0], fw_pad])
         state = {L: list(plan["init_state"][L]) for L in ("prior", "post", "fp")}
         tape = {}
 
@@ -2793,21 +2795,10 @@ class NormRecurrentCore(torch.autograd.Function):
         h_prior_all = run_layer("prior", 1, run_layer("prior", 0, prior_all))
         h_post_all = run_layer("post", 1, run_layer("post", 0, post_all))
         # posterior head + reparameterisation, then the frame predictor's input conv, once over all steps
-        sp = stream_ptr()
-        slabs, split, stride = conv_forward_split(h_post_all, None, head_w, want_slabs=True)
-        call("rac_slab_reduce2", ptr(slabs), split, stride, ptr(head_b), ptr(mu_all), ptr(lv_all), T * M, 2 * z, z, None, None, sp)
-        eps_stack = torch.stack(eps_all)
-        zs = torch.empty_like(mu_all)
-        call("rac_reparam_fwd", ptr(mu_all), ptr(lv_all), ptr(eps_stack), ptr(zs), zs.numel(), sp)
+        zs, eps_stack = _posterior_sample(h_post_all, head, eps_all, mu_all, lv_all)
         vs = plan["vs"]
-        v3 = [torch.cat([vs[t][k] for t in range(T)]) if k < len(vs[0]) else None for k in range(3)]
-        cat = torch.empty((T * B, H, W, ct + pad), device=dev, dtype=torch.float32)
-        slot = amax_slot(dev)
-        call("rac_tilecat_fwd", ptr(v3[0]), v3[0].shape[1] if v3[0] is not None else 0, ptr(v3[1]),
-             v3[1].shape[1] if v3[1] is not None else 0, ptr(v3[2]), v3[2].shape[1] if v3[2] is not None else 0,
-             ptr(h_all), g, ptr(zs), z, pad, ptr(cat), T * B, H * W, ptr(slot), 0, sp)
-        tag_amax(cat, slot)
-        xf_all = conv_forward_split(cat, None, fw_pad, fconv.bias)
+        v_all = [torch.cat([vs[t][k] for t in range(T)]) for k in range(len(vs[0]))]
+        cat, xf_all = _frame_input(v_all, h_all, zs, lambda: fw_pad, fconv.bias)
         h_pred_all = run_layer("fp", 1, run_layer("fp", 0, xf_all))
         ctx.plan = {k: plan[k] for k in ("g", "z", "nv", "cells", "head", "frame_conv")}
         ctx.tape = tape
@@ -2824,22 +2815,15 @@ class NormRecurrentCore(torch.autograd.Function):
         g, z, nv = plan["g"], plan["z"], plan["nv"]
         M, HW = B * H * W, H * W
         dev = ctx.lv_all.device
-        cells, fconv = plan["cells"], plan["frame_conv"]
-        head_w, head_b = plan["head"]
+        cells, fconv, head = plan["cells"], plan["frame_conv"], plan["head"]
         ct = nv + g + z
         cpad = ct + (-ct) % 32
         fw_pad = padded_weight(fconv.weight, cpad)
         cont = lambda t_: None if t_ is None else t_.contiguous()
         d_hpred, d_mu, d_lv, d_hprior = cont(d_hpred), cont(d_mu), cont(d_lv), cont(d_hprior)
-        for L in ("prior", "post", "fp"):
-            for cell in cells[L]:
-                weight_parts(cell.ih_gates[0].weight, transposed=True), weight_parts(cell.hh_gates[0].weight, transposed=True)
-        weight_parts(head_w, transposed=True), weight_parts(fw_pad, transposed=True)
+        chain_ws = lambda L, extra: _norm_chain_ws(cells[L]) + extra
+        _refresh_parts(chain_ws("prior", []) + chain_ws("post", []) + chain_ws("fp", [head[0], fw_pad]), transposed=True)
         sp = stream_ptr()
-
-        def window(slabs, n, cin, t, col=0):  # rows of step t of batched slabs [n][T M][cin] as a gradient source
-            rows = slabs.view(n, T, M, cin)[0, t]
-            return (rows, n, slabs.numel() // n if n > 1 else 0, cin, col)
 
         def layer_bwd(L, l, ext):
             """Backward of all T steps of one layer; `ext(t)` = the sources of dh[t] from outside the layer's own recurrence.
@@ -2886,40 +2870,29 @@ class NormRecurrentCore(torch.autograd.Function):
             bias_grad_acc(dg_ih_all, ci.bias)
             return dx_slabs, n_x
 
-        def chain_ws(L, extra):
-            return [c_.ih_gates[0].weight for c_ in cells[L]] + [c_.hh_gates[0].weight for c_ in cells[L]] + extra
-
         # ---- frame predictor
         hp_s = None if d_hpred is None else d_hpred.view((T, B) + tuple(d_hpred.shape[1:]))
         top, n_top = layer_bwd("fp", 1, lambda t: [_src(hp_s[t], 1, g)] if hp_s is not None else [])
-        low, n_low = layer_bwd("fp", 0, lambda t: [window(top, n_top, g, t)])
+        low, n_low = layer_bwd("fp", 0, lambda t: [_step_rows(top, n_top, g, T, M, t)])
         dy_f_all = torch.empty((T * B, H, W, g), device=dev, dtype=torch.float32)
         slot_f = amax_slot(dev)
         tag_amax(grad_sum([_src(low, n_low, g, 0)], dy_f_all, g, slot_f), slot_f)
-        dcat, n_c = conv_dgrad_slabs(dy_f_all, fw_pad, cpad)
-        conv_wgrad_split_acc(dy_f_all, thin["cat"], None, fconv.weight, defer=True)  # un-pads into weight.grad
-        bias_grad_acc(dy_f_all, fconv.bias)
-        d_h_all = grad_sum([_src(dcat, n_c, cpad, nv)], torch.empty((T * B, H, W, g), device=dev, dtype=torch.float32), g)
+        d_h_all = torch.empty((T * B, H, W, g), device=dev, dtype=torch.float32)
+        dcat, n_c = _frame_input_bwd(dy_f_all, thin["cat"], fw_pad, fconv, d_h_all, nv)
         flush_deferred_wgrads_early(chain_ws("fp", [fconv.weight]))
         # ---- posterior: reparameterisation + KL gradients -> merged head -> the two layers
-        dy_h = torch.empty((T * B, H, W, 2 * z), device=dev, dtype=torch.float32)
-        slot = amax_slot(dev)
-        call("rac_reparam_head_bwd", _pack_srcs([_src(dcat, n_c, cpad, nv + g)]), 1, ptr(ctx.lv_all), ptr(thin["eps"]),
-             ptr(d_mu), ptr(d_lv), ptr(dy_h), T * M, z, ptr(slot), sp)
-        tag_amax(dy_h, slot)
-        dhead, n_h = conv_dgrad_slabs(dy_h, head_w, g)
-        conv_wgrad_split_acc(dy_h, tag_amax(thin["h_post"], amax_one(dev)), None, head_w, defer=True)
-        bias_grad_acc(dy_h, head_b)
-        top, n_top = layer_bwd("post", 1, lambda t: [window(dhead, n_h, g, t)])
-        low, n_low = layer_bwd("post", 0, lambda t: [window(top, n_top, g, t)])
+        dhead, n_h = _posterior_head_bwd(_src(dcat, n_c, cpad, nv + g), ctx.lv_all, thin["eps"], d_mu, d_lv,
+                                         tag_amax(thin["h_post"], amax_one(dev)), head)
+        top, n_top = layer_bwd("post", 1, lambda t: [_step_rows(dhead, n_h, g, T, M, t)])
+        low, n_low = layer_bwd("post", 0, lambda t: [_step_rows(top, n_top, g, T, M, t)])
         slot_post = amax_slot(dev)
         d_post_all = tag_amax(grad_sum([_src(low, n_low, g, 0)], torch.empty((T * B, H, W, g), device=dev, dtype=torch.float32),
                                        g, slot_post), slot_post)
-        flush_deferred_wgrads_early(chain_ws("post", [head_w]))
+        flush_deferred_wgrads_early(chain_ws("post", [head[0]]))
         # ---- prior (its z is not used on this path: only its hidden state feeds the batched mu_p / logvar_p heads)
         hq_s = None if d_hprior is None else d_hprior.view((T, B) + tuple(d_hprior.shape[1:]))
         top, n_top = layer_bwd("prior", 1, lambda t: [_src(hq_s[t], 1, g)] if hq_s is not None else [])
-        low, n_low = layer_bwd("prior", 0, lambda t: [window(top, n_top, g, t)])
+        low, n_low = layer_bwd("prior", 0, lambda t: [_step_rows(top, n_top, g, T, M, t)])
         slot_prior = amax_slot(dev)
         d_prior_all = tag_amax(grad_sum([_src(low, n_low, g, 0)], torch.empty((T * B, H, W, g), device=dev, dtype=torch.float32),
                                         g, slot_prior), slot_prior)
