@@ -468,6 +468,40 @@ int rac_predict_frames(const float* x4, const float* prev, const float* target, 
                        uint8_t* gen_u8, uint8_t* true_u8, int64_t image_stride, int32_t n, int32_t nt, int32_t H,
                        int32_t W, void* stream);
 
+/* The image half of the data path (data.py ImagePipeline; robonet_dataset.py:257-300,545-572) in one launch: the raw
+ * uint8 frames and 0 / 1 masks of a batch of B videos of T frames -> images (T, B, 3, h, w) and out_masks (T, B, 1, h, w),
+ * fp32, contiguous, time first.  Per output pixel, with the host pipeline's fp32 expressions (one rounding per operation):
+ *   1. u8 / 255 (a true division), resized bilinearly from the video's (Hs, Ws) to (h, w) by torch's align_corners=False
+ *      rule: scale = (float)in / out, src = max(scale * (o + 0.5f) - 0.5f, 0), i0 = (int)src, i1 = i0 + (i0 < in - 1),
+ *      l1 = src - i0, l0 = 1 - l1; value = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11).
+ *      (Hs, Ws) == (h, w): the identity.
+ *   2. when (th, tw) != (h, w): the same rule from the th x tw window at (top, left) of image 1 back to (h, w); each
+ *      of its four taps evaluates 1 in place (no intermediate image).
+ *   3. masks: the same geometry on the 0 / 1 mask, 1.0f where the result is non-zero.
+ *   4. when `jitter` != 0: the four colour steps in the order `order[0..3]` (0 brightness x * f0; 1 contrast
+ *      f1 * x + (1 - f1) * mean(gray) over the frame as it stands; 2 saturation f2 * x + (1 - f2) * gray; 3 hue shift by
+ *      f3 through hsv), brightness / contrast / saturation clamped to [0, 1], gray = 0.2989 r + 0.587 g + 0.114 b.
+ *      `factor` holds the drawn Python floats: the kernel rounds f and (1 - f) to fp32 as torch rounds its scalars.
+ * frame_offset / mask_offset: bytes from `frames` / `masks` to the video's (T, Hs, Ws, 3) / (T, Hs, Ws) block, so one
+ * flat buffer holds videos of different raw sizes.  `jobs` is an array of B jobs in DEVICE memory (8-byte aligned).
+ * w % 4 == 0 (float4 stores), h, w <= 128, any Hs, Ws >= 1, 0 <= top, top + th <= h (likewise left / tw), outputs 16-byte
+ * aligned.  One workgroup per frame; the contrast mean is summed in a fixed order (no atomics): the same bits on
+ * every run.  The jobs live in device memory, so this call cannot inspect them: the CALLER checks that every job's
+ * offsets, (Hs, Ws) and T stay inside `frames` / `masks` and that its window lies inside (h, w) (data.py _image_jobs does);
+ * the kernel only keeps its taps inside the frame a job describes.
+ * rac_image_job_bytes() = sizeof(rac_image_job), for bindings that mirror the struct. */
+typedef struct rac_image_job {
+  int64_t frame_offset, mask_offset;
+  int32_t Hs, Ws, top, left, th, tw;
+  int32_t order[4];
+  int32_t jitter;
+  int32_t reserved;
+  double factor[4]; /* brightness, contrast, saturation, hue */
+} rac_image_job;
+int rac_image_job_bytes(void);
+int rac_image_pipeline(const uint8_t* frames, const uint8_t* masks, const rac_image_job* jobs, float* images,
+                       float* out_masks, int32_t B, int32_t T, int32_t h, int32_t w, void* stream);
+
 /* The deterministic baselines (dynamics.py:341-454).
  * rac_det_pack_fwd: the ConvLSTM input of DeterministicConvModel in one launch, out [B][HW][Gp]:
  *   channels [0, g) = enc[b][p][:]; g + ch (ch 0, 1) = ba[ch*HW + p] + sum_k wa[ch*HW + p][k] * action[b][k]

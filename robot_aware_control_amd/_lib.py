@@ -62,6 +62,13 @@ class OptimRange(C.Structure):
     _fields_ = [("begin4", i64), ("n4", i64), ("block_begin", i64), ("amax", vp)]
 
 
+class ImageJob(C.Structure):
+    """struct rac_image_job (include/rac_hip.h): one video of a rac_image_pipeline launch."""
+    _fields_ = [("frame_offset", i64), ("mask_offset", i64), ("Hs", i32), ("Ws", i32), ("top", i32), ("left", i32),
+                ("th", i32), ("tw", i32), ("order", i32 * 4), ("jitter", i32), ("reserved", i32),
+                ("factor", C.c_double * 4)]
+
+
 OPTIM_RMSPROP, OPTIM_SGD = 0, 1            # RAC_OPTIM_* rules
 OPTIM_NESTEROV, OPTIM_FIRST_STEP = 1, 2    # RAC_OPTIM_* flags
 
@@ -149,6 +156,8 @@ _SIGS = {
     "rac_composite_fwd": [vp, vp, vp, i32, i32, vp],
     "rac_composite_bwd": [vp, vp, vp, vp, vp, i32, i32, vp],
     "rac_predict_frames": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
+    "rac_image_job_bytes": [],
+    "rac_image_pipeline": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "rac_det_pack_fwd": [vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp],
     "rac_det_pack_bwd": [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp],
     "rac_copy_baseline": [vp, vp, vp, vp, i32, i32, vp],

@@ -13,7 +13,11 @@ What is different, for a trainer that consumes ~2 800 frames/s per GPU:
     transposed to time-first there while the current step computes (the reference transposes on the host and copies on
     the compute stream);
   * trajectory files may be HDF5 (`h5py`, imported when the first `.hdf5` file is opened) or `.npz` archives with the
-    same dataset names (the format of `tools/make_synthetic_robonet.py`, used by the tests: this container has no h5py).
+    same dataset names (the format of `tools/make_synthetic_robonet.py`, used by the tests: this container has no h5py);
+  * `--device_images True` (off by default) moves the image half of an item to the GPU: the dataset hands over the raw
+    uint8 frames, the binary raw masks and the augmentation parameters it drew (`draw_image_params`), `collate` packs a
+    batch's videos (of any raw sizes) into one flat uint8 buffer plus one `rac_image_job` per video, and one
+    `rac_image_pipeline` launch on the prefetcher's stream writes the time-first fp32 `images` / `masks`.
 """
 from __future__ import annotations
 
@@ -22,11 +26,14 @@ import pickle
 import random
 import threading
 from queue import Queue
+from typing import NamedTuple
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 import torch.utils.data as data
+
+from . import _lib
 
 TRANSPOSE_KEYS = ("qpos", "images", "states", "actions", "masks", "heatmaps", "raw_actions", "raw_states")
 
@@ -140,25 +147,91 @@ def _adjust_hue(img, factor):
     return sel.gather(2, idx).squeeze(2)
 
 
+JITTER_RANGES = ((0.8, 1.2), (0.8, 1.2), (0.8, 1.2), (-0.1, 0.1))  # brightness, contrast, saturation, hue
+
+
+def draw_color_jitter(brightness, contrast, saturation, hue):
+    """The random part of get_random_color_jitter (robonet_dataset.py:545-572): the four factors drawn with
+    `random.uniform` in the order brightness, contrast, saturation, hue, then one `random.shuffle` of the four
+    operations.  Returns (factors, order): operation order[k] runs k-th, 0 = brightness .. 3 = hue."""
+    factors = tuple(random.uniform(*r) for r in (brightness, contrast, saturation, hue))
+    order = [0, 1, 2, 3]
+    random.shuffle(order)
+    return factors, tuple(order)
+
+
+def color_jitter(factors, order):
+    """The function of a (T,3,H,W) clip that applies drawn jitter parameters in the drawn order (brightness, contrast and
+    saturation clamped to [0, 1], the hue shift through hsv)."""
+    bf, cf, sf, hf = factors
+    ops = (lambda im: (im * bf).clamp(0, 1),
+           lambda im: (cf * im + (1 - cf) * _gray(im).mean((1, 2, 3), keepdim=True)).clamp(0, 1),
+           lambda im: (sf * im + (1 - sf) * _gray(im)).clamp(0, 1),
+           lambda im: _adjust_hue(im, hf))
+
+    def apply(im):
+        for k in order:
+            im = ops[k](im)
+        return im
+    return apply
+
+
 def random_color_jitter(brightness, contrast, saturation, hue):
     """get_random_color_jitter (robonet_dataset.py:545-572): factors drawn with `random.uniform` in this order, the
     four adjustments applied in a `random.shuffle`d order; returns a function of a (T,3,H,W) clip."""
-    ops = []
-    bf = random.uniform(*brightness)
-    ops.append(lambda im: (im * bf).clamp(0, 1))
-    cf = random.uniform(*contrast)
-    ops.append(lambda im: (cf * im + (1 - cf) * _gray(im).mean((1, 2, 3), keepdim=True)).clamp(0, 1))
-    sf = random.uniform(*saturation)
-    ops.append(lambda im: (sf * im + (1 - sf) * _gray(im)).clamp(0, 1))
-    hf = random.uniform(*hue)
-    ops.append(lambda im: _adjust_hue(im, hf))
-    random.shuffle(ops)
+    return color_jitter(*draw_color_jitter(brightness, contrast, saturation, hue))
 
-    def apply(im):
-        for op in ops:
-            im = op(im)
-        return im
-    return apply
+
+class ImageParams(NamedTuple):
+    """What `ImagePipeline` decides at random for one trajectory, apart from its application: the crop window
+    (top, left, th, tw) of the (h, w) model-size clip that is resized back to (h, w) -- the whole clip without
+    augmentation -- and, when `jitter`, the colour factors (brightness, contrast, saturation, hue) and the order of the
+    four operations (order[k] runs k-th; 0 = brightness, 1 = contrast, 2 = saturation, 3 = hue)."""
+    h: int
+    w: int
+    top: int
+    left: int
+    th: int
+    tw: int
+    jitter: bool
+    order: tuple
+    factors: tuple
+
+
+def draw_image_params(h: int, w: int, augment: bool) -> ImageParams:
+    """Draws one trajectory's augmentation from the `random` and torch generators exactly as the reference's item code
+    does (robonet_dataset.py:271-300): `random.randint(0, 5)` for the shrink, the crop corner from the torch generator
+    (row first, only when the shrink is non-zero), then the colour jitter's draws."""
+    if not augment:
+        return ImageParams(h, w, 0, 0, h, w, False, (0, 1, 2, 3), (1.0, 1.0, 1.0, 0.0))
+    shrink = random.randint(0, 5)
+    th, tw = h - shrink, w - shrink
+    top = left = 0
+    if shrink:  # tf.RandomCrop.get_params draws the corner from the torch generator, row first
+        top = int(torch.randint(0, h - th + 1, size=(1,)).item())
+        left = int(torch.randint(0, w - tw + 1, size=(1,)).item())
+    factors, order = draw_color_jitter(*JITTER_RANGES)
+    return ImageParams(h, w, top, left, th, tw, True, order, factors)
+
+
+def apply_image_params(frames, masks, p: ImageParams):
+    """uint8 frames (T,Hs,Ws,3) and masks (T,Hs,Ws) of a window -> (T,3,h,w) images, (T,1,h,w) binary masks, on the host
+    in fp32: ToTensor + one bilinear resize of the whole window, the crop resized back, the jitter.  Masks may be the
+    file's float values or the device mode's uint8 `mask != 0`: raw masks are non-negative, so both are non-zero at
+    the same output pixels."""
+    if isinstance(masks, torch.Tensor):
+        masks = masks.numpy()
+    if isinstance(frames, torch.Tensor):
+        frames = frames.numpy()
+    video = _resize(_to_tensor(frames), p.h, p.w)
+    mask = _resize(_to_tensor(masks.astype(np.float32)), p.h, p.w)
+    if p.jitter or (p.th, p.tw) != (p.h, p.w):
+        window = (slice(None), slice(None), slice(p.top, p.top + p.th), slice(p.left, p.left + p.tw))
+        video = _resize(video[window], p.h, p.w)
+        mask = _resize(mask[window], p.h, p.w)
+    if p.jitter:
+        video = color_jitter(p.factors, p.order)(video)
+    return video, mask.type(torch.bool).type(torch.float32)
 
 
 # --------------------------------------------------------------------------- #
@@ -282,31 +355,30 @@ class ImagePipeline:
     def __init__(self, height: int, width: int, augment: bool):
         self.h, self.w, self.augment = height, width, augment
 
+    def draw(self) -> ImageParams:
+        return draw_image_params(self.h, self.w, self.augment)
+
     def __call__(self, frames, masks):
-        video = _resize(_to_tensor(frames), self.h, self.w)
-        mask = _resize(_to_tensor(masks), self.h, self.w)
-        if self.augment:
-            shrink = random.randint(0, 5)
-            th, tw = self.h - shrink, self.w - shrink
-            top = left = 0
-            if shrink:  # tf.RandomCrop.get_params draws the corner from the torch generator, row first
-                top = int(torch.randint(0, self.h - th + 1, size=(1,)).item())
-                left = int(torch.randint(0, self.w - tw + 1, size=(1,)).item())
-            jitter = random_color_jitter((0.8, 1.2), (0.8, 1.2), (0.8, 1.2), (-0.1, 0.1))
-            window = (slice(None), slice(None), slice(top, top + th), slice(left, left + tw))
-            video = jitter(_resize(video[window], self.h, self.w))
-            mask = _resize(mask[window], self.h, self.w)
-        return video, mask.type(torch.bool).type(torch.float32)
+        return apply_image_params(frames, masks, self.draw())
 
 
 class RoboNetDataset(data.Dataset):
     """Trajectory files -> the reference's item dict (robonet_dataset.py:23-171): images (T,3,h,w) in [0,1], states (T,R)
     normalised, actions (T-1,A), masks (T,1,h,w) in {0,1}, qpos (T,Q), robot, folder, file_path, idx (+ low / high /
-    raw_* for finetune_* experiments, high_movement with --load_movement_info)."""
+    raw_* for finetune_* experiments, high_movement with --load_movement_info).
 
-    def __init__(self, hdf5_list, robot_list, config, augment_img=False, load_snippet=False, rng_seed=None):
+    `device_images=True`: instead of `images` / `masks` an item carries what the device needs to make them
+    (`rac_image_pipeline`, through `collate` and `process_batch` / the prefetcher): `frames` uint8 (T,Hs,Ws,3) as
+    stored, `raw_masks` uint8 (T,Hs,Ws) = `mask != 0` (raw masks are non-negative, so the resized mask is non-zero
+    exactly where the resized `mask != 0` is) and `image_params`, the `ImageParams` drawn for this trajectory from the
+    same random streams at the same point.  Every other key, the window sampling and the `preload_ram` cache are
+    unchanged; a cached item keeps its parameters as a cached host item keeps its augmented frames."""
+
+    def __init__(self, hdf5_list, robot_list, config, augment_img=False, load_snippet=False, rng_seed=None,
+                 device_images=False):
         self._traj_names, self._traj_robots = hdf5_list, robot_list
         self._config = config
+        self._device_images = bool(device_images)
         self._data_root = config.data_root
         self._video_length = (config.n_past + config.n_future) if load_snippet else config.video_length
         self._action_dim = config.action_dim
@@ -368,7 +440,8 @@ class RoboNetDataset(data.Dataset):
             masks_key = "masks" if "masks" in traj else "mask"
             s, e = self._window(traj[frames_key].shape[0], path)
             frames = traj[frames_key][s:e]
-            masks = traj[masks_key][s:e].astype(np.float32)
+            masks = traj[masks_key][s:e]
+            masks = (masks != 0).astype(np.uint8) if self._device_images else masks.astype(np.float32)
             raw_low, raw_high = pipe.view.bounds(traj)
             raw_states = fit_width(traj["states"][s:e].astype(np.float32), cf.robot_dim)
             raw_actions = self.read_actions(traj, s, e - 1, raw_low[4], raw_high[4])
@@ -380,11 +453,18 @@ class RoboNetDataset(data.Dataset):
         if getattr(cf, "model_use_heatmap", False):
             raise NotImplementedError  # as the reference (robonet_dataset.py:130-133)
         low, high = pipe.bounds(raw_low, raw_high)
-        images, masks = self._images(frames, masks)
+        if self._device_images:
+            if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[-1] != 3:
+                raise ValueError(f"{path}: device_images needs uint8 (T,H,W,3) frames, got {frames.dtype} {frames.shape}")
+            pictures = {"frames": torch.from_numpy(np.ascontiguousarray(frames))}
+            mask_keys = {"raw_masks": torch.from_numpy(masks), "image_params": self._images.draw()}
+        else:
+            images, masks = self._images(frames, masks)
+            pictures, mask_keys = {"images": images}, {"masks": masks}
         states = pipe.states(raw_states, low, high)
         actions = pipe.actions(states, raw_actions, low, high)
         folder = os.path.basename(os.path.dirname(name))
-        item = {"images": images, "states": states, "actions": actions, "masks": masks, "robot": robot, "folder": folder,
+        item = {**pictures, "states": states, "actions": actions, **mask_keys, "robot": robot, "folder": folder,
                 "file_path": path, "idx": idx, "qpos": qpos}
         if "finetune" in cf.experiment:  # the robot model of finetune_* windows needs the bounds (:148-166)
             item["low"], item["high"] = low, high
@@ -433,9 +513,94 @@ def split_files(config):
                             random_state=np.random.RandomState(config.seed))
 
 
+RAW_IMAGE_KEYS = ("frames", "raw_masks", "image_jobs", "image_shape")  # of a collated device_images batch
+IMAGE_JOB = np.dtype(_lib.ImageJob)  # struct rac_image_job as a numpy record
+
+
 def collate(items):
-    """Default collation of the item dicts (tensors / arrays stacked, strings listed), images already float."""
-    return data.default_collate(items)
+    """Default collation of the item dicts (tensors / arrays stacked, strings listed), images already float.
+    Items of a `device_images` dataset: their raw videos may differ in size (RoboNet's 240x320 next to the authors' own
+    rigs), so the bytes of all `frames` go into ONE flat uint8 buffer, all `raw_masks` into another, and `image_jobs`
+    (B, sizeof(rac_image_job)) uint8 holds one job per video: its byte offsets into the two buffers, its (Hs, Ws) and
+    its `ImageParams`; `image_shape` = (T, h, w)."""
+    if "frames" not in items[0]:
+        return data.default_collate(items)
+    out = data.default_collate([{k: v for k, v in it.items() if k not in ("frames", "raw_masks", "image_params")}
+                                for it in items])
+    p0, T = items[0]["image_params"], items[0]["frames"].shape[0]
+    jobs = np.zeros(len(items), IMAGE_JOB)
+    f_off = m_off = 0
+    for job, it in zip(jobs, items):
+        fr, mk, p = it["frames"], it["raw_masks"], it["image_params"]
+        if fr.shape[0] != T or tuple(mk.shape) != tuple(fr.shape[:3]) or (p.h, p.w) != (p0.h, p0.w):
+            raise ValueError(f"device_images batch: {tuple(fr.shape)} frames, {tuple(mk.shape)} masks, T {T}")
+        job["frame_offset"], job["mask_offset"] = f_off, m_off
+        job["Hs"], job["Ws"] = fr.shape[1], fr.shape[2]
+        job["top"], job["left"], job["th"], job["tw"] = p.top, p.left, p.th, p.tw
+        job["order"], job["factor"], job["jitter"] = p.order, p.factors, int(p.jitter)
+        f_off += fr.numel()
+        m_off += mk.numel()
+    out["frames"] = torch.cat([it["frames"].reshape(-1) for it in items])
+    out["raw_masks"] = torch.cat([it["raw_masks"].reshape(-1) for it in items])
+    out["image_jobs"] = torch.from_numpy(jobs.view(np.uint8).reshape(len(items), IMAGE_JOB.itemsize))
+    out["image_shape"] = torch.tensor([T, p0.h, p0.w])
+    return out
+
+
+def _image_jobs(batch):
+    """The job records of a collated device_images batch, checked against the buffers they index."""
+    jobs = batch["image_jobs"].numpy().reshape(-1).view(IMAGE_JOB)
+    T, h, w = (int(v) for v in batch["image_shape"])
+    for j in jobs:
+        n = T * int(j["Hs"]) * int(j["Ws"])
+        ok = (j["Hs"] >= 1 and j["Ws"] >= 1 and j["frame_offset"] >= 0 and j["mask_offset"] >= 0
+              and j["frame_offset"] + 3 * n <= batch["frames"].numel() and j["mask_offset"] + n <= batch["raw_masks"].numel()
+              and j["th"] >= 1 and j["tw"] >= 1 and j["top"] >= 0 and j["left"] >= 0
+              and j["top"] + j["th"] <= h and j["left"] + j["tw"] <= w and sorted(j["order"]) == [0, 1, 2, 3])
+        if not ok:
+            raise ValueError(f"device_images batch: job {j} does not fit its buffers / the {h}x{w} model size")
+    return jobs, T, h, w
+
+
+def host_images(batch):
+    """`images` (B,T,3,h,w) / `masks` (B,T,1,h,w) of a collated device_images batch by the HOST pipeline
+    (`apply_image_params` per video): what the batch would have held with device_images off, bit for bit."""
+    jobs, T, h, w = _image_jobs(batch)
+    frames, masks = batch["frames"].numpy(), batch["raw_masks"].numpy()
+    images, out_masks = [], []
+    for j in jobs:
+        im, mk = apply_image_params(*job_video(j, frames, masks, T), job_params(j, h, w))
+        images.append(im)
+        out_masks.append(mk)
+    return torch.stack(images), torch.stack(out_masks)
+
+
+def job_params(j, h, w) -> ImageParams:
+    """The `ImageParams` a job record was made from."""
+    return ImageParams(h, w, int(j["top"]), int(j["left"]), int(j["th"]), int(j["tw"]), bool(j["jitter"]),
+                       tuple(int(k) for k in j["order"]), tuple(float(f) for f in j["factor"]))
+
+
+def job_video(j, frames, masks, T):
+    """A job's (T,Hs,Ws,3) frames and (T,Hs,Ws) masks as views of the flat numpy buffers."""
+    Hs, Ws, n = int(j["Hs"]), int(j["Ws"]), T * int(j["Hs"]) * int(j["Ws"])
+    return (frames[j["frame_offset"]:j["frame_offset"] + 3 * n].reshape(T, Hs, Ws, 3),
+            masks[j["mask_offset"]:j["mask_offset"] + n].reshape(T, Hs, Ws))
+
+
+def device_images(batch, device):
+    """Time-first `images` (T,B,3,h,w) / `masks` (T,B,1,h,w) of a collated device_images batch on `device`: the raw
+    buffers and the job array are uploaded and ONE `rac_image_pipeline` launch does the rest, all on the current
+    stream.  Also returns the tensors that launch reads (host and device), for the caller to keep until it has run."""
+    jobs, T, h, w = _image_jobs(batch)
+    host = [t if t.is_pinned() else t.pin_memory() for t in (batch["frames"], batch["raw_masks"], batch["image_jobs"])]
+    frames, masks, jobs_dev = (t.to(device, non_blocking=True) for t in host)
+    B = len(jobs)
+    images = torch.empty(T, B, 3, h, w, device=device)
+    out_masks = torch.empty(T, B, 1, h, w, device=device)
+    _lib.call("rac_image_pipeline", _lib.ptr(frames), _lib.ptr(masks), _lib.ptr(jobs_dev), _lib.ptr(images),
+              _lib.ptr(out_masks), B, T, h, w, _lib.stream_ptr())
+    return images, out_masks, host + [frames, masks, jobs_dev]
 
 
 def _dist_info():
@@ -452,10 +617,11 @@ def create_loaders(config):
     on identical batches and the gradient all-reduce would average copies of one gradient."""
     X_train, X_test, y_train, y_test = split_files(config)
     world, rank = _dist_info()
+    on_device = getattr(config, "device_images", False)
     train_data = RoboNetDataset(X_train, y_train, config, augment_img=getattr(config, "img_augmentation", False),
-                                rng_seed=config.seed + rank if world > 1 else None)
-    test_data = RoboNetDataset(X_test, y_test, config)
-    common = dict(num_workers=config.data_threads, drop_last=False, pin_memory=True,
+                                rng_seed=config.seed + rank if world > 1 else None, device_images=on_device)
+    test_data = RoboNetDataset(X_test, y_test, config, device_images=on_device)
+    common = dict(num_workers=config.data_threads, drop_last=False, pin_memory=True, collate_fn=collate,
                   persistent_workers=config.data_threads > 0)
     if world > 1:
         sampler = data.distributed.DistributedSampler(train_data, num_replicas=world, rank=rank, shuffle=True,
@@ -492,7 +658,7 @@ def _locobot_files(config):
 
 def _plain_loader(ds, config, batch_size):
     return data.DataLoader(ds, num_workers=config.data_threads, batch_size=batch_size, shuffle=True, drop_last=False,
-                           pin_memory=True, generator=torch.Generator().manual_seed(config.seed),
+                           pin_memory=True, generator=torch.Generator().manual_seed(config.seed), collate_fn=collate,
                            persistent_workers=config.data_threads > 0)
 
 
@@ -502,7 +668,8 @@ def create_transfer_loader(config, n_files: int = 400):
     files, labels = _locobot_files(config)
     if not files:
         return None
-    ds = RoboNetDataset(files[:n_files], labels[:n_files], config, augment_img=getattr(config, "img_augmentation", False))
+    ds = RoboNetDataset(files[:n_files], labels[:n_files], config, augment_img=getattr(config, "img_augmentation", False),
+                        device_images=getattr(config, "device_images", False))
     return _plain_loader(ds, config, config.batch_size)
 
 
@@ -511,9 +678,10 @@ def create_finetune_loaders(config):
     (locobot_singleview_dataloader.py:12-57)."""
     files, labels = _locobot_files(config)
     n_test, n_train = config.finetune_num_test, config.finetune_num_train
+    on_device = getattr(config, "device_images", False)
     train = RoboNetDataset(files[n_test:n_test + n_train], labels[n_test:n_test + n_train], config,
-                           augment_img=getattr(config, "img_augmentation", False))
-    test = RoboNetDataset(files[:n_test], labels[:n_test], config)
+                           augment_img=getattr(config, "img_augmentation", False), device_images=on_device)
+    test = RoboNetDataset(files[:n_test], labels[:n_test], config, device_images=on_device)
     return _plain_loader(train, config, config.batch_size), _plain_loader(test, config, config.test_batch_size)
 
 
@@ -527,10 +695,24 @@ def _start_epoch(loader, epoch: int):
 # host -> device
 # --------------------------------------------------------------------------- #
 def process_batch(data: dict, device) -> dict:
-    """Changes tensor idx from batch-first to time-first and moves it to `device` (robonet_dataset.py:434-451)."""
+    """Changes tensor idx from batch-first to time-first and moves it to `device` (robonet_dataset.py:434-451).
+    A `device_images` batch gets its `images` / `masks` here: from `rac_image_pipeline` on a GPU, from the host pipeline
+    on the CPU (the same tensors as with device_images off)."""
+    if "frames" in data:
+        if torch.device(device).type == "cuda":
+            with torch.cuda.device(device):
+                images, masks, _ = device_images(data, device)  # (the current stream orders the buffers' reuse)
+        else:
+            images, masks = (t.transpose(0, 1) for t in host_images(data))
+        for k in RAW_IMAGE_KEYS:
+            del data[k]
+        pictures = {"images": images, "masks": masks}
+    else:
+        pictures = {}
     for k in TRANSPOSE_KEYS:
         if k in data:
             data[k] = data[k].transpose_(1, 0).to(device, non_blocking=True)
+    data.update(pictures)
     return data
 
 
@@ -543,20 +725,28 @@ class DevicePrefetcher:
         self.loader, self.device = loader, torch.device(device)
         self.stream = torch.cuda.Stream(self.device)
         self.q: Queue = Queue(maxsize=depth)
+        self._raw = []  # (event, tensors): raw image buffers of uploads whose kernel may not have run yet
         self._stop = False
         self.thread = threading.Thread(target=self._run, daemon=True)
         self.thread.start()
 
     def _upload(self, batch):
         out = dict(batch)
+        raw = None
         with torch.cuda.stream(self.stream):
+            if "frames" in out:  # a device_images batch: upload the raw bytes + jobs, one launch makes images / masks
+                out["images"], out["masks"], raw = device_images(out, self.device)
+                for k in RAW_IMAGE_KEYS:
+                    del out[k]
             for k in TRANSPOSE_KEYS:
-                if k in out:
+                if k in out and not (raw is not None and k in ("images", "masks")):  # (those are time-first already)
                     t = out[k]
                     t = t if t.is_pinned() else t.pin_memory()
                     out[k] = t.to(self.device, non_blocking=True).transpose(0, 1).contiguous()
             ev = torch.cuda.Event()
             ev.record(self.stream)
+        if raw is not None:  # keep what the launch reads until the event says it has run
+            self._raw = [(e, r) for e, r in self._raw if not e.query()] + [(ev, raw)]
         return out, ev
 
     def _run(self):
