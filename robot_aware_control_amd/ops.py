@@ -325,8 +325,8 @@ def bias_grad_acc(dy, bias):
     """bias.grad += column sums of dy.  Inside `deferred_wgrad()` the few-row tensors of the recurrent part are only
     recorded: one launch per bias sums all its time steps when the context exits."""
     M = dy.numel() // dy.shape[-1]
-    if _DEFERRED is not None and M <= _COLSUM_STEPS_MAX_ROWS:
-        _DEFERRED_BIAS.setdefault(id(bias), (bias, []))[1].append(dy)
+    if _WINDOW is not None and M <= _COLSUM_STEPS_MAX_ROWS:
+        _WINDOW.biases.setdefault(id(bias), (bias, []))[1].append(dy)
         return
     call("rac_colsum_acc", ptr(dy), ptr(grad_buffer(bias)), ptr(_colsum_parts(dy.device, M, dy.shape[-1])), M,
          dy.shape[-1], stream_ptr())
@@ -339,22 +339,6 @@ def _colsum_parts(device, M: int, Cc: int):
 
 
 _COLSUM_STEPS_MAX_ROWS = 16384
-_DEFERRED_BIAS = {}
-
-
-def _flush_bias_grads():
-    pending = dict(_DEFERRED_BIAS)
-    _DEFERRED_BIAS.clear()
-    sp = stream_ptr()
-    for bias, dys in pending.values():
-        g = grad_buffer(bias)
-        Cc = dys[0].shape[-1]
-        M = dys[0].numel() // Cc
-        for lo in range(0, len(dys), _lib.WGRAD_MAX_STEPS):
-            chunk = dys[lo:lo + _lib.WGRAD_MAX_STEPS]
-            assert all(d.shape == dys[0].shape and d.is_contiguous() for d in chunk)
-            xs = (C.c_void_p * len(chunk))(*[ptr(d) for d in chunk])
-            call("rac_colsum_steps", xs, len(chunk), ptr(g), ptr(_colsum_parts(g.device, M, Cc)), M, Cc, sp)
 
 
 # --------------------------------------------------------------------------- #
@@ -523,8 +507,8 @@ def _wp_upload(jobs, device):
     return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
 
 
-_ADAM_SIDE = {"stream": None}  # fused_adam_step(late=...): the late weights' update runs here
-ADAM_LATE_WGS = int(os.environ.get("RAC_ADAM_LATE_WGS", "512"))  # ... on this many workgroups (2 per CU)
+# fused_adam_step(late=...): the late weights' update runs on _side_stream("adam"), on this many workgroups (2 per CU)
+ADAM_LATE_WGS = int(os.environ.get("RAC_ADAM_LATE_WGS", "512"))
 ADAM_WGS = int(os.environ.get("RAC_ADAM_WGS", "0"))  # (experiments: the one-stream pass on a bounded grid too; 0 = one workgroup per block)
 
 
@@ -791,9 +775,7 @@ def fused_adam_step(flat, grad, m, v, lr, beta1, beta2, eps, step, late=None):
     done = []
     if n_late:
         main = torch.cuda.current_stream()
-        if _ADAM_SIDE["stream"] is None or _ADAM_SIDE["stream"].device != dev:
-            _ADAM_SIDE["stream"] = torch.cuda.Stream(device=dev)
-        side = _ADAM_SIDE["stream"]
+        side = _side_stream("adam", dev)  # the late weights' update runs here
         ready = torch.cuda.Event()
         ready.record(main)  # every gradient, the scale bounds and whatever read the old weights precede the side launch
         side.wait_event(ready)
@@ -1129,7 +1111,6 @@ def conv_dgrad_split(dy, weight, C0: int, C1: int = 0, need1: bool = True):
 # applied at every time step (the ConvLSTM gate convs, the input convs) is not launched per step; its (dy, x0, x1)
 # triples are kept and ONE launch over all steps' pixels runs when the context exits (one read-modify-write of the
 # gradient instead of T, longer K loops).  Same sum, different association across steps.
-_DEFERRED = None
 DEFER_WGRAD = os.environ.get("RAC_DEFER_WGRAD", "1") == "1"
 WGRAD_PRESPLIT = os.environ.get("RAC_WGRAD_PRESPLIT", "1") == "1"
 # workgroups that stage one operand tile before splitting it once pays
@@ -1145,14 +1126,19 @@ WGRAD_ALLKY = os.environ.get("RAC_WGRAD_ALLKY", "1") == "1"
 # waits for them before anything reads a gradient (all-reduce, Adam).  RAC_WGRAD_STREAM=0: on the main stream, at the end.
 WGRAD_STREAM = os.environ.get("RAC_WGRAD_STREAM", "1") == "1"
 WGRAD_CHAIN_FLUSH = os.environ.get("RAC_WGRAD_CHAIN_FLUSH", "1") == "1"  # per ConvLSTM chain (0: once, behind the core)
-_SIDE = {"stream": None, "done": None, "keep": [], "on_ready": None}
+# a window whose encoder / decoder ran per step records the vgg layers' weight gradients per step too (vgg_steps)
+VGG_WGRAD_BATCH = os.environ.get("RAC_VGG_WGRAD_BATCH", "1") == "1"
+_STREAMS = {}
+_WINDOW = None  # the live _WgradWindow (inside `deferred_wgrad()`), or None
 
 
-def _side_stream(dev):
-    """The stream the weight gradients run on, beside the data-gradient chain."""
-    st = _SIDE["stream"]
-    if st is None or st.device != torch.device(dev):
-        st = _SIDE["stream"] = torch.cuda.Stream(device=dev)
+def _side_stream(name, dev):
+    """The device's side stream of that name, made at its first use: "wgrad" (the weight gradients, beside the
+    data-gradient chain), "adam" (fused_adam_step's late update), "prior" / "post" (_ChainRegion)."""
+    key = (name, dev if isinstance(dev, torch.device) else torch.device(dev))
+    st = _STREAMS.get(key)
+    if st is None:
+        st = _STREAMS[key] = torch.cuda.Stream(device=dev)
     return st
 
 
@@ -1166,155 +1152,171 @@ def _amax_reserve(device, n: int) -> None:
             _AMAX["used"] = 0
 
 
-def flush_deferred_wgrads_early(weights=None, final=True) -> None:
+def _operand_maxima(tensors) -> None:
+    """The operands' maxima on the CURRENT stream, before a launch that reads them is forked to the side stream (a
+    reduction launched there would leave a tag this stream's consumers could read unordered)."""
+    for t in tensors:
+        if t is not None:
+            amax_for(t)
+
+
+class _WgradWindow:
+    """What one `deferred_wgrad()` context holds.  One-stream rule: a parameter's launches all read-modify-write its .grad
+    and only stream order keeps them apart: once one went to the side stream, none goes to the main stream before `join`.
+    The rule is checked for what is RECORDED here (`launch`); what `wgrad_on_side_stream` forks is opaque to it."""
+
+    def __init__(self, on_ready, flush_after, vgg_steps):
+        early = bool(flush_after) and flush_after > 0 and WGRAD_STREAM and WGRAD_CHAIN_FLUSH
+        self.weights = {}  # id(weight) -> (weight, [(dy, x0, x1), ..]): recorded, not launched yet
+        self.biases = {}   # id(bias) -> (bias, [dy, ..]): the same for the column sums
+        self.flush_after = int(flush_after) if early else None  # step count at which a weight's records go to the side stream
+        self.seen = {}     # id(weight) -> steps recorded for it so far in this window (launched ones included)
+        self.ready_done = set()  # weights handed to `on_ready` (their reduction may be running): no more records
+        self.vgg_steps = bool(vgg_steps) and early and VGG_WGRAD_BATCH
+        self.on_ready = on_ready
+        self.on_side = set()  # parameters with a launch on the side stream
+        self.done = None      # the side stream's last event: `join` makes the main stream wait for it
+        self.keep = []        # what the side stream's launches read, referenced until then
+
+    def record(self, dy, x0, x1, weight) -> None:
+        if id(weight) in self.ready_done:
+            raise _lib.RacError("a weight gradient was recorded after the weight's data-parallel reduction had started "
+                                "(more steps than deferred_wgrad's flush_after counted on)")
+        recs = self.weights.setdefault(id(weight), (weight, []))[1]
+        recs.append((dy, x0, x1))
+        seen = self.seen[id(weight)] = self.seen.get(id(weight), 0) + 1
+        if seen == self.flush_after:
+            _operand_maxima([dy, x0, x1] + [t for rec in recs[:-1] for t in rec])
+            flush_deferred_wgrads_early([weight])
+
+    def fork(self, run, keep, dev, amax_slots: int) -> None:
+        """`run()` on the side stream, behind everything enqueued so far on the current one."""
+        _amax_reserve(dev, amax_slots)
+        main = torch.cuda.current_stream()
+        side = _side_stream("wgrad", dev)
+        ready = torch.cuda.Event()
+        ready.record(main)
+        side.wait_event(ready)  # everything enqueued so far (the operands) precedes the side stream's launches
+        with torch.cuda.stream(side):
+            try:
+                run()
+            finally:
+                # the operands were allocated on the main stream: they stay referenced until it has been made to wait for
+                # `done` (join) -- only then may the allocator hand their memory to later main-stream kernels
+                self.keep.append(keep)
+                self.done = torch.cuda.Event()
+                self.done.record(side)
+
+    def launch(self, items, biases, side: bool) -> None:
+        """One time-batched launch per (weight, records) and per (bias, records), on the current stream (`side`: the side one)."""
+        ids = [id(w) for w, _ in items] + list(biases)
+        if side:
+            self.on_side.update(ids)
+        elif not self.on_side.isdisjoint(ids):
+            raise _lib.RacError("a gradient launched on the side stream earlier in this deferred_wgrad() was recorded "
+                                "again and would be accumulated on the main stream before the two are joined")
+        # largest first: their all-reduces are the longest and overlap the remaining launches
+        # (ties broken by address: every data-parallel rank issues its all-reduces in the same order)
+        for weight, recs in sorted(items, key=lambda wi: (-wi[0].numel(), wi[0].data_ptr())):
+            _wgrad_split_batch(recs, weight)
+            if self.on_ready is not None:
+                self.ready_done.add(id(weight))
+                self.on_ready(weight)  # (a collective started here orders itself behind the current stream)
+        sp = stream_ptr()
+        for bias, dys in biases.values():
+            g = grad_buffer(bias)
+            Cc = dys[0].shape[-1]
+            M = dys[0].numel() // Cc
+            for lo in range(0, len(dys), _lib.WGRAD_MAX_STEPS):
+                chunk = dys[lo:lo + _lib.WGRAD_MAX_STEPS]
+                assert all(d.shape == dys[0].shape and d.is_contiguous() for d in chunk)
+                xs = (C.c_void_p * len(chunk))(*[ptr(d) for d in chunk])
+                call("rac_colsum_steps", xs, len(chunk), ptr(g), ptr(_colsum_parts(g.device, M, Cc)), M, Cc, sp)
+
+    def flush_early(self, weights) -> None:
+        if weights is None:  # everything recorded so far (each record's operands exist: produced in program order)
+            items = list(self.weights.values())
+            self.weights.clear()
+        else:
+            items = [self.weights.pop(id(w)) for w in weights if id(w) in self.weights]
+        if not items and (weights is not None or not self.biases):
+            return
+        biases, self.biases = self.biases, {}
+        dev = items[0][0].device if items else next(iter(biases.values()))[0].device
+        self.fork(lambda: self.launch(items, biases, side=True), (items, biases), dev, 8192)
+
+    def close(self) -> None:
+        global _WINDOW
+        if self.flush_after is not None and (self.weights or self.biases):
+            # the rest of what was launched early goes to the SAME stream (the one-stream rule)
+            flush_deferred_wgrads_early(None)  # (also when only bias column sums are left)
+        _WINDOW = None  # (a record made under the leftovers' launches or `on_ready` is launched at once)
+        items, self.weights = list(self.weights.values()), {}
+        biases, self.biases = self.biases, {}
+        self.launch(items, biases, side=False)
+
+    def join(self) -> None:
+        if self.done is not None:  # (also on an exception: nothing may outlive the side stream's reads)
+            torch.cuda.current_stream().wait_event(self.done)
+
+
+def flush_deferred_wgrads_early(weights=None) -> None:
     """Launch the recorded (deferred) weight gradients of `weights` (None: all recorded so far), and the bias column sums
-    recorded so far, NOW on the side stream.  Called where their last operand was produced (RecurrentCore.backward).
-    `final`: nothing more will be recorded for these weights -- `on_ready` (the data-parallel reduction of a weight's
-    gradient slice) may start behind the launch; a weight that records again afterwards raises."""
-    if _DEFERRED is None or not WGRAD_STREAM or (weights is not None and not WGRAD_CHAIN_FLUSH):
+    recorded so far, NOW on the side stream.  Called where their last operand was produced (RecurrentCore.backward):
+    nothing more will be recorded for these weights -- `on_ready` (the data-parallel reduction of a weight's gradient
+    slice) may start behind the launch; a weight that records again afterwards raises."""
+    if _WINDOW is None or not WGRAD_STREAM or (weights is not None and not WGRAD_CHAIN_FLUSH):
         return
-    if weights is None:  # everything recorded so far (each record's operands exist: they were produced in program order)
-        items = list(_DEFERRED.values())
-        bias_only = not items and bool(_DEFERRED_BIAS)
-        _DEFERRED.clear()
-    else:
-        items = [_DEFERRED.pop(id(w)) for w in weights if id(w) in _DEFERRED]
-        bias_only = False
-    if not items and not bias_only:
-        return
-    dev = items[0][0].device if items else next(iter(_DEFERRED_BIAS.values()))[0].device
-    _amax_reserve(dev, 8192)
-    main = torch.cuda.current_stream()
-    side = _side_stream(dev)
-    ready = torch.cuda.Event()
-    ready.record(main)
-    side.wait_event(ready)  # everything enqueued so far (the operands) precedes the side stream's launches
-    bias_pending = dict(_DEFERRED_BIAS)
-    with torch.cuda.stream(side):
-        for weight, its in sorted(items, key=lambda wi: (-wi[0].numel(), wi[0].data_ptr())):
-            _wgrad_split_batch(its, weight)
-            if _SIDE["on_ready"] is not None and final:
-                _READY_DONE.add(id(weight))
-                _SIDE["on_ready"](weight)  # (a collective started here orders itself behind the side stream)
-        _flush_bias_grads()
-        done = torch.cuda.Event()
-        done.record(side)
-    # the operands were allocated on the main stream: they stay referenced until the main stream has been made to wait
-    # for `done` (deferred_wgrad's exit) -- only then may the allocator hand their memory to later main-stream kernels
-    _SIDE["keep"].append((items, bias_pending))
-    _SIDE["done"] = done
+    _WINDOW.flush_early(weights)
 
 
 def wgrad_on_side_stream(launch, operands, need_amax=True) -> None:
     """Run one layer's weight-gradient launch(es) on the side stream (inside `deferred_wgrad()` only: its exit is where the
     main stream waits): the data-gradient chain of the backward pass goes on without them.  `operands`: the tensors the
-    launch reads -- their operand maxima are taken on the main stream first (a reduction launched on the side stream
-    would leave a tag the main stream may consume unordered), and they stay referenced until the main stream has waited."""
-    if _DEFERRED is None or not WGRAD_STREAM or not operands[0].is_cuda:
+    launch reads -- their maxima are taken on the main stream first, and they stay referenced until it has waited."""
+    if _WINDOW is None or not WGRAD_STREAM or not operands[0].is_cuda:
         launch()
         return
     if need_amax:
-        for t in operands:
-            if t is not None:
-                amax_for(t)
-    _amax_reserve(operands[0].device, 64)
-    main = torch.cuda.current_stream()
-    dev = operands[0].device
-    side = _side_stream(dev)
-    ready = torch.cuda.Event()
-    ready.record(main)
-    side.wait_event(ready)
-    with torch.cuda.stream(side):
-        launch()
-        done = torch.cuda.Event()
-        done.record(side)
-    _SIDE["keep"].append(operands)
-    _SIDE["done"] = done
-
-
-_FLUSH_AFTER = None  # deferred_wgrad(flush_after=n | (n1, n2, ..)): a weight's records are launched (side stream) whenever
-_FLUSH_SEEN = {}     # the number of steps recorded for it so far (counted here) reaches one of these
-_READY_DONE = set()  # weights whose gradient slice was handed to `on_ready` (its reduction may be running): no more records
-_VGG_STEPS = False   # ... and the vgg layers' weight gradients are recorded per step too (the encoder / decoder ran per step)
-VGG_WGRAD_BATCH = os.environ.get("RAC_VGG_WGRAD_BATCH", "1") == "1"
+        _operand_maxima(operands)
+    _WINDOW.fork(launch, operands, operands[0].device, 64)
 
 
 @contextlib.contextmanager
 def deferred_wgrad(on_ready=None, flush_after=None, vgg_steps=False):
     """`on_ready(weight)` is called after each weight's batched launch is enqueued (its gradient is then complete
     in stream order): the trainer starts that slice's data-parallel all-reduce there.
-    `flush_after` = n or (n1, n2, ..) (the per-step autograd path of a T-step window: T): whenever a weight has that many
-    recorded steps, what is recorded is launched -- time-batched -- on the side stream, under the rest of the backward pass
-    (which walks the window from its last step to its first): with T a weight's launch starts the moment its last operand
-    exists, instead of behind the whole pass, where 4.8 ms stood exposed at cfg2 with every frame fed back
-    (profiles/r06a_*).  Measured at cfg2, every frame fed back, same-day boxes: at exit 1.586 x the teacher-forced step, T
-    1.469 x (3.5 ms still exposed: every weight completes inside the last fifth of the pass), (T - 1, T) 1.536 x -- the
-    earlier launches take from the latency-bound data-gradient chain more than they hide.  Whatever is left follows when
-    the context exits, on the same stream.  The hand-scheduled core launches its chains' gradients itself.
+    `flush_after` = n (the per-step autograd path of a T-step window: T): when a weight has that many recorded steps,
+    what is recorded is launched -- time-batched -- on the side stream, under the rest of the backward pass (which walks
+    the window from its last step to its first): with T a weight's launch starts the moment its last operand exists,
+    instead of behind the whole pass, where 4.8 ms stood exposed at cfg2 with every frame fed back (profiles/r06a_*).
+    Measured at cfg2, every frame fed back, same-day boxes: at exit 1.586 x the teacher-forced step, T 1.469 x (3.5 ms
+    still exposed: every weight completes inside the last fifth of the pass), the two flush points (T - 1, T) 1.536 x --
+    the earlier launches take from the latency-bound data-gradient chain more than they hide (the tuple form is gone:
+    tools/experiments/README.md).  Whatever is left follows when the context exits, on the same stream.  The
+    hand-scheduled core launches its chains' gradients itself.
     `vgg_steps`: the encoder and the decoder ran once per step too (a window that feeds predicted frames back): their
     layers' weight gradients are time-batched the same way -- one launch over n steps' pixels instead of n launches of a
-    fifth of the rows each (0.06-0.12 of the pipe at 16 images per launch)."""
-    global _DEFERRED, _FLUSH_AFTER, _VGG_STEPS
-    if not DEFER_WGRAD or _DEFERRED is not None:
+    fifth of the rows each (0.06-0.12 of the pipe at 16 images per launch).
+    A nested context records into the outer one; RAC_DEFER_WGRAD=0: no window, every gradient is launched at once."""
+    global _WINDOW
+    if not DEFER_WGRAD or _WINDOW is not None:
         yield
         return
-    _DEFERRED = {}
-    if flush_after and WGRAD_STREAM and WGRAD_CHAIN_FLUSH:
-        pts = (flush_after,) if isinstance(flush_after, int) else tuple(flush_after)
-        _FLUSH_AFTER = frozenset(int(v) for v in pts if v and v > 0) or None
-    else:
-        _FLUSH_AFTER = None
-    _FLUSH_SEEN.clear()
-    _READY_DONE.clear()
-    _VGG_STEPS = bool(vgg_steps) and _FLUSH_AFTER is not None and VGG_WGRAD_BATCH
-    _SIDE["on_ready"] = on_ready
+    window = _WINDOW = _WgradWindow(on_ready, flush_after, vgg_steps)
     try:
         yield
-        if _FLUSH_AFTER is not None and (_DEFERRED or _DEFERRED_BIAS):
-            # the rest of what was launched early goes to the SAME stream: a weight's (and a bias's) two launches both
-            # read-modify-write its gradient, and only stream order keeps them apart
-            flush_deferred_wgrads_early(None)  # (also when only bias column sums are left)
-        pending, _DEFERRED = _DEFERRED, None
-        # largest first: their all-reduces are the longest and overlap the remaining launches
-        # (ties broken by address: every data-parallel rank issues its all-reduces in the same order)
-        for weight, items in sorted(pending.values(), key=lambda wi: (-wi[0].numel(), wi[0].data_ptr())):
-            _wgrad_split_batch(items, weight)
-            if on_ready is not None:
-                on_ready(weight)
-        _flush_bias_grads()
+        window.close()
     finally:
-        _DEFERRED = None
-        _FLUSH_AFTER = None
-        _READY_DONE.clear()
-        _VGG_STEPS = False
-        _DEFERRED_BIAS.clear()
-        if _SIDE["done"] is not None:  # (also on an exception: nothing may outlive the side stream's reads)
-            torch.cuda.current_stream().wait_event(_SIDE["done"])
-            _SIDE["done"] = None
-        _SIDE["keep"].clear()
-        _SIDE["on_ready"] = None
+        _WINDOW = None
+        window.join()
 
 
 def conv_wgrad_split_acc(dy, x0, x1, weight, defer=False):
     """weight.grad += dW on the split-precision pipe.
     `defer`: inside `deferred_wgrad()` only record the operands (the caller must not modify them afterwards)."""
-    if defer and _DEFERRED is not None:
-        if id(weight) in _READY_DONE:
-            raise _lib.RacError("a weight gradient was recorded after the weight's data-parallel reduction had started "
-                                "(more steps than deferred_wgrad's flush_after counted on)")
-        rec = _DEFERRED.setdefault(id(weight), (weight, []))[1]
-        rec.append((dy, x0, x1))
-        seen = _FLUSH_SEEN[id(weight)] = _FLUSH_SEEN.get(id(weight), 0) + 1
-        if _FLUSH_AFTER is not None and seen in _FLUSH_AFTER:
-            for t_ in (dy, x0, x1):  # operand maxima on THIS stream (a reduction launched on the side stream would leave a
-                if t_ is not None:   # tag this stream's consumers could read unordered)
-                    amax_for(t_)
-            for dy_, x0_, x1_ in rec[:-1]:
-                for t_ in (dy_, x0_, x1_):
-                    if t_ is not None:
-                        amax_for(t_)
-            # (only the last flush point may start the weight's reduction: earlier ones leave steps to come)
-            flush_deferred_wgrads_early([weight], final=seen == max(_FLUSH_AFTER))
+    if defer and _WINDOW is not None:
+        _WINDOW.record(dy, x0, x1, weight)
         return
     _wgrad_split_batch([(dy, x0, x1)], weight)
 
@@ -1784,7 +1786,7 @@ class VggLayer(torch.autograd.Function):
                 else:
                     conv_wgrad_acc(draw, x0, x1, weight)
             # (the layer's weight gradient leaves the data-gradient chain: side stream, see deferred_wgrad)
-            if _VGG_STEPS and split and not padded and wgrad_split_ok(x0, x1, weight):
+            if _WINDOW is not None and _WINDOW.vgg_steps and split and not padded and wgrad_split_ok(x0, x1, weight):
                 conv_wgrad_split_acc(draw, x0, x1, weight, defer=True)  # one launch over the window's steps
             else:
                 wgrad_on_side_stream(wgrad, (draw, x0, x1), need_amax=split)
@@ -2222,7 +2224,6 @@ def recurrent_core_ok(h_all, g: int, z: int, nv: int, cells, head, frame_conv) -
 CHAIN_STREAMS = os.environ.get("RAC_CHAIN_STREAMS", "0") == "1"
 CORE_LAYER_MAJOR = os.environ.get("RAC_CORE_LAYER_MAJOR", "1") == "1"  # a layer's T launches back to back (RecurrentCore)
 CORE_BATCH_THIN = os.environ.get("RAC_CORE_BATCH_THIN", "1") == "1"    # ... and the thin convs between the chains once over all steps
-_CHAIN = {"dev": None, "prior": None, "post": None}
 
 
 class _ChainRegion:
@@ -2236,9 +2237,7 @@ class _ChainRegion:
         self.streams = {}
         if not self.enabled:
             return
-        if _CHAIN["dev"] != torch.device(dev):
-            _CHAIN.update(dev=torch.device(dev), prior=torch.cuda.Stream(device=dev), post=torch.cuda.Stream(device=dev))
-        self.streams = {"prior": _CHAIN["prior"], "post": _CHAIN["post"]}
+        self.streams = {name: _side_stream(name, dev) for name in ("prior", "post")}
         _amax_reserve(dev, 16384)  # no fresh (kernel-zeroed) amax arena inside the region
         start = torch.cuda.Event()
         start.record(self.main)
