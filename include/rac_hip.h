@@ -645,6 +645,39 @@ int rac_optim_ranges(float* p, const float* g, float* state0, float* state1, con
                      int32_t n_ranges, int64_t total_blocks, int32_t rule, int32_t flags, float lr, float momentum,
                      float gain, float alpha, float eps, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * The learned robot model (--learned_robot_model): JointPosPredictor and GripperStatePredictor
+ * (src/prediction/models/dynamics.py:269-338), both  in -> 512 -> 512 -> 512 -> D  with ReLU after the first three
+ * layers, in = D + A (D = robot_joint_dim or robot_dim, 1..7; A = action_dim, 1..5).
+ * A model's parameters are ONE contiguous, 16-byte aligned fp32 block in state_dict order with torch's [out][in] layout:
+ *   W1[512][D+A], b1[512], W2[512][512], b2[512], W3[512][512], b3[512], W4[D][512], b4[D]
+ * (rac_mlp4_param_count floats; negative for dimensions outside the ranges above); a gradient block has the same layout.
+ * Exact fp32: the 512x512 layers on v_mfma_f32_16x16x4_f32, the thin layers on fmaf.  A row's result depends on the
+ * row alone -- fixed K order per output element, no split K, no float atomics -- so it is the same bits in any batch.
+ * ------------------------------------------------------------------------ */
+int64_t rac_mlp4_param_count(int32_t D, int32_t A);
+/* y[M][D] = MLP([x | a]) (+ x with `residual`), x[M][D], a[M][A]; the concat is never materialised.
+ * acts: NULL, or [3][M][512] receiving the three post-ReLU activations (what rac_mlp4_bwd reads). */
+int rac_mlp4_fwd(const float* params, const float* x, const float* a, float* y, float* acts, int64_t M, int32_t D,
+                 int32_t A, int32_t residual, void* stream);
+/* Both models' residual rollouts in ONE launch (trainer.py:205-229), the loop over steps inside the kernel:
+ *   q_out[0] = q0, q_out[t+1] = q_out[t] + joint(q_out[t] | actions[t])        q0[N][J], q_out[T+1][N][J]
+ *   s_out[0] = s0, s_out[t+1] = s_out[t] + gripper(s_out[t] | actions[t])      s0[N][R], s_out[T+1][N][R]
+ * actions[T][N][A].  Either parameter block may be NULL (that model is skipped, its arrays unused).  Step t gives the
+ * bits of rac_mlp4_fwd(residual = 1) on the rollout's step t - 1 output. */
+int rac_robot_rollout(const float* joint_params, const float* gripper_params, const float* q0, const float* s0,
+                      const float* actions, float* q_out, float* s_out, int32_t T, int64_t N, int32_t J, int32_t R,
+                      int32_t A, void* stream);
+/* Parameter gradients of y = MLP([x | a]) from dy[M][D], the inputs and the activations rac_mlp4_fwd saved:
+ * a per-tile dgrad chain writes the pre-activation gradients dz[3][M][512] (scratch the caller provides), then one launch
+ * computes dW_k = dz_k^T h_{k-1} (each workgroup walks all M rows in order) and the bias gradients (column sums, in
+ * order).  accumulate = 1: grads += result, 0: grads = result.  Input gradients are not computed. */
+int rac_mlp4_bwd(const float* params, const float* x, const float* a, const float* acts, const float* dy, float* dz,
+                 float* grads, int64_t M, int32_t D, int32_t A, int32_t accumulate, void* stream);
+/* loss[0] = scale * sum_i (pred[i] - target[i])^2 and, with dy != NULL, dy[i] = 2 scale (pred[i] - target[i]);
+ * a fixed summation order (joint_pos_trainer.py:173-211 with its steps batched as rows: scale = 1 / (B D)). */
+int rac_mse_rows(const float* pred, const float* target, float scale, float* loss, float* dy, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

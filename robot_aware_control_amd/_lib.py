@@ -175,12 +175,17 @@ _SIGS = {
     "rac_adam_ranges": [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, i32, vp],
     "rac_optim_step": [vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, f32, vp],
     "rac_optim_ranges": [vp, vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, f32, f32, f32, vp],
+    "rac_mlp4_param_count": [i32, i32],
+    "rac_mlp4_fwd": [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
+    "rac_robot_rollout": [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, i32, vp],
+    "rac_mlp4_bwd": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
+    "rac_mse_rows": [vp, vp, f32, vp, vp, i64, vp],
     "rac_version": [],
     "rac_device_arch": [],
     "rac_last_error": [],
 }
 _RET = {"rac_device_arch": C.c_char_p, "rac_last_error": C.c_char_p, "rac_absmax_blocks": i64, "rac_colsum_blocks": i64,
-        "rac_weight_frag_blocks": i64}
+        "rac_weight_frag_blocks": i64, "rac_mlp4_param_count": i64}
 EXPORTS = tuple(_SIGS)
 
 _lib = None

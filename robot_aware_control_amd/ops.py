@@ -3250,3 +3250,125 @@ def to_map(planes: torch.Tensor) -> torch.Tensor:
 def to_planes_view(m: torch.Tensor) -> torch.Tensor:
     """(B,H,W,C) map -> logical (B,C,H,W) view (channels_last strides, no copy)."""
     return m.permute(0, 3, 1, 2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The learned robot model's 4-layer MLPs (csrc/rac_mlp.hip; reference dynamics.py:269-338).  `params` / `grads` are a
+# model's contiguous parameter and gradient blocks (robot_model._Mlp4Predictor.flat_parameters()).
+MLP_HIDDEN = 512
+
+
+def _rows(t: torch.Tensor, width: int, what: str) -> torch.Tensor:
+    _require_cuda(t)
+    if t.dim() != 2 or t.shape[1] != width or t.dtype != torch.float32:
+        raise ValueError(f"{what}: expected a float32 (rows, {width}) tensor, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def mlp4_forward(params, x, a, residual=False, save=False):
+    """y = MLP([x | a]) (+ x with `residual`); with `save` also the [3][M][512] post-ReLU activations for mlp4_backward."""
+    _require_cuda(params)
+    D, A = x.shape[-1], a.shape[-1]
+    x, a = _rows(x, D, "mlp4_forward x"), _rows(a, A, "mlp4_forward action")
+    M = x.shape[0]
+    if a.shape[0] != M:
+        raise ValueError(f"mlp4_forward: {M} state rows but {a.shape[0]} action rows")
+    y = torch.empty((M, D), device=x.device, dtype=torch.float32)
+    acts = torch.empty((3, M, MLP_HIDDEN), device=x.device, dtype=torch.float32) if save else None
+    if M:
+        call("rac_mlp4_fwd", ptr(params), ptr(x), ptr(a), ptr(y), ptr(acts), M, D, A, int(bool(residual)), stream_ptr())
+    return y, acts
+
+
+def mlp4_backward(params, grads, x, a, acts, dy, accumulate=True):
+    """Parameter gradients into the block `grads` (added to it, or overwriting it); no input gradients."""
+    D, A = x.shape[-1], a.shape[-1]
+    x, a, dy = _rows(x, D, "mlp4_backward x"), _rows(a, A, "mlp4_backward action"), _rows(dy, D, "mlp4_backward dy")
+    M = x.shape[0]
+    if not M:
+        if not accumulate:
+            grads.zero_()
+        return
+    dz = torch.empty((3, M, MLP_HIDDEN), device=x.device, dtype=torch.float32)
+    call("rac_mlp4_bwd", ptr(params), ptr(x), ptr(a), ptr(acts), ptr(dy), ptr(dz), ptr(grads), M, D, A,
+         int(bool(accumulate)), stream_ptr())
+
+
+def robot_rollout(joint_params, gripper_params, q0, s0, actions):
+    """(q[T+1][N][J], s[T+1][N][R]) of the two residual recurrences in one launch; a model passed as None is skipped and
+    its result is None."""
+    T, N, A = actions.shape
+    _require_cuda(actions)
+    actions = actions.contiguous()
+    q = s = None
+    J = R = 0
+    if joint_params is not None:
+        J = q0.shape[-1]
+        q0 = _rows(q0, J, "robot_rollout qpos")
+        q = torch.empty((T + 1, N, J), device=actions.device, dtype=torch.float32)
+    if gripper_params is not None:
+        R = s0.shape[-1]
+        s0 = _rows(s0, R, "robot_rollout state")
+        s = torch.empty((T + 1, N, R), device=actions.device, dtype=torch.float32)
+    for start in (q0 if q is not None else None, s0 if s is not None else None):
+        if start is not None and start.shape[0] != N:
+            raise ValueError(f"robot_rollout: {start.shape[0]} start rows but {N} action rows")
+    if actions.dtype != torch.float32:
+        raise ValueError("robot_rollout: float32 actions")
+    call("rac_robot_rollout", ptr(joint_params), ptr(gripper_params), ptr(q0) if q is not None else None,
+         ptr(s0) if s is not None else None, ptr(actions), ptr(q), ptr(s), T, N, J, R, A, stream_ptr())
+    return q, s
+
+
+def mse_rows(pred, target, scale, loss=None, want_grad=False):
+    """loss[0] = scale * sum (pred - target)^2 into `loss` (a 1-element device tensor or view, allocated if None), and
+    with `want_grad` dy = 2 scale (pred - target).  Returns (loss, dy)."""
+    _require_cuda(pred)
+    pred, target = pred.contiguous(), target.contiguous()
+    if pred.shape != target.shape or pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError(f"mse_rows: float32 tensors of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    if loss is None:
+        loss = torch.empty((1,), device=pred.device, dtype=torch.float32)
+    dy = torch.empty_like(pred) if want_grad else None
+    call("rac_mse_rows", ptr(pred), ptr(target), float(scale), ptr(loss), ptr(dy), pred.numel(), stream_ptr())
+    return loss, dy
+
+
+class Mlp4(torch.autograd.Function):
+    """delta = MLP([x | a]) of one predictor (dynamics.py:290-302, :326-338).  `anchor` is one of the model's parameters: it
+    carries requires_grad into the tape; the parameter gradients are accumulated into the model's gradient block by the
+    kernels, so every autograd output is None.  Inputs that require grad are refused (the reference trains teacher-forced:
+    no input gradient is ever needed, and none is built)."""
+
+    @staticmethod
+    def forward(ctx, x, a, anchor, params, grads):
+        if x.requires_grad or a.requires_grad:
+            raise ValueError("Mlp4: inputs that require grad are not supported (no input-gradient kernel is built)")
+        save = ctx.needs_input_grad[2]  # the anchor requires grad and the call site records a tape
+        y, acts = mlp4_forward(params, x, a, residual=False, save=save)
+        if save:
+            ctx.save_for_backward(x, a, acts)
+            ctx.blocks = (params, grads)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, a, acts = ctx.saved_tensors
+        params, grads = ctx.blocks
+        mlp4_backward(params, grads, x, a, acts, dy.contiguous(), accumulate=True)
+        return None, None, None, None, None
+
+
+class MseRows(torch.autograd.Function):
+    """nn.MSELoss() of (pred, target) as a (1,) tensor (losses.py mse_criterion), with its gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        loss, dy = mse_rows(pred, target, 1.0 / pred.numel(), want_grad=True)
+        ctx.save_for_backward(dy)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        (dy,) = ctx.saved_tensors
+        return dy * gout, None

@@ -1,0 +1,258 @@
+"""The learned robot model (`--learned_robot_model True --robot_model_ckpt <ckpt>`): robot states and masks of the
+finetune_* experiments from two small MLPs instead of an analytical model.
+
+`JointPosPredictor` and `GripperStatePredictor` are the reference's modules (src/prediction/models/dynamics.py:269-338):
+`in -> 512 -> 512 -> 512 -> D` with ReLU after the first three layers, `forward(x, action)` returns the DELTA and the
+caller adds the residual, `state_dict` keys `predictor.{0,2,4,6}.{weight,bias}`.  Here a model's parameters are views of
+ONE contiguous block in state_dict order with torch's [out][in] layout
+
+    W1[512][D+A], b1[512], W2[512][512], b2[512], W3[512][512], b3[512], W4[D][512], b4[D]
+
+(and their gradients views of a second block), which is what the kernels of csrc/rac_mlp.hip read: forward, backward and
+the T-step residual rollout of both models in one launch.  `RobotModels` puts both models into one buffer so that the
+fused optimisers (optim.make_optimizer) step them in one launch, with a state dict interchangeable with a torch.optim one
+over `list(joint.parameters()) + list(gripper.parameters())` (joint_pos_trainer.py:98-101).
+
+`LearnedRobotModel` has `PredictionTrainer.robot_model`'s contract: `predict_batch(batch) -> (states, masks)` is the
+reference's `_generate_learned_robot_states` (trainer.py:164-257) -- the whole window is rolled out in one launch, the
+predicted joint positions come to the host in one copy, the masks are rendered (MuJoCo, on the CPU: any object with the
+reference mask envs' `generate_masks(list_of_qpos)`), resized to the frames' size as the reference resizes them, and go
+back in one upload.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib, ops
+
+HIDDEN = ops.MLP_HIDDEN
+MAX_STATE_DIM, MAX_ACTION_DIM = 7, 5  # rac_mlp4_* (include/rac_hip.h)
+
+
+def param_count(D: int, A: int) -> int:
+    return HIDDEN * (D + A) + HIDDEN + 2 * (HIDDEN * HIDDEN + HIDDEN) + D * HIDDEN + D
+
+
+class _Mlp4Predictor(nn.Module):
+    _dim_field = None
+
+    def __init__(self, config):
+        super().__init__()
+        D, A = int(getattr(config, self._dim_field)), int(config.action_dim)
+        if not (1 <= D <= MAX_STATE_DIM and 1 <= A <= MAX_ACTION_DIM):
+            raise ValueError(f"{type(self).__name__}: {self._dim_field} in 1..{MAX_STATE_DIM} and action_dim in "
+                             f"1..{MAX_ACTION_DIM} are built on the HIP path (got {D}, {A})")
+        self.state_dim, self.action_dim = D, A
+        # torch's default nn.Linear initialisation on the CPU, in the reference's order (it applies no init_weights to
+        # these models): the same seed gives the same initial weights
+        self.predictor = nn.Sequential(
+            nn.Linear(D + A, HIDDEN), nn.ReLU(inplace=True), nn.Linear(HIDDEN, HIDDEN), nn.ReLU(inplace=True),
+            nn.Linear(HIDDEN, HIDDEN), nn.ReLU(inplace=True), nn.Linear(HIDDEN, D))
+        self._flatten()
+
+    def numel(self) -> int:
+        return param_count(self.state_dim, self.action_dim)
+
+    def _flatten(self, flat=None, grad=None, base=0):
+        """Re-home every parameter as a view of one block (and its .grad of another): the blocks are this model's own, or
+        the slice [base, base + numel) of a container's buffers."""
+        params = list(self.parameters())  # state_dict order
+        n = self.numel()
+        if flat is None:
+            dev = params[0].device
+            flat = torch.zeros((n + 3) // 4 * 4, device=dev, dtype=torch.float32)
+            grad = torch.zeros_like(flat)
+        off = base
+        with torch.no_grad():
+            for p in params:
+                view = flat[off:off + p.numel()].view(p.shape)
+                if view.data_ptr() != p.data_ptr():
+                    view.copy_(p.data)
+                    p.data = view
+                p.grad = grad[off:off + p.numel()].view(p.shape)
+                p._rac_off = off  # the parameter's place in the buffer the optimiser steps (optim._views)
+                off += p.numel()
+        assert off - base == n
+        self._root = (flat, grad)
+        self._flat, self._flat_grad = flat[base:base + n], grad[base:base + n]
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        self._flatten()
+        return out
+
+    def flat_parameters(self):
+        """(parameter block, gradient block) in the layout of the module docstring."""
+        p0 = self.predictor[0].weight
+        if p0.data_ptr() != self._flat.data_ptr() or p0.grad is None or p0.grad.data_ptr() != self._flat_grad.data_ptr():
+            self._flatten(*self._root, base=self._flat.storage_offset() - self._root[0].storage_offset())
+        return self._flat, self._flat_grad
+
+    def zero_grad(self, set_to_none: bool = False):
+        """The kernels accumulate into the gradient block: zero it and keep the views attached."""
+        _, grad = self.flat_parameters()
+        grad.zero_()
+
+    def forward(self, x, action):
+        """The difference between the next and the current state after applying `action` (dynamics.py:290-302)."""
+        if not (x.is_cuda and action.is_cuda and self._flat.is_cuda):
+            raise _lib.RacError(f"{type(self).__name__} runs on the GPU only (no CPU fallback)")
+        flat, grad = self.flat_parameters()
+        return ops.Mlp4.apply(x, action, self.predictor[0].weight, flat, grad)
+
+
+class JointPosPredictor(_Mlp4Predictor):
+    """Predicts the change of the robot's joint positions (dynamics.py:269-302)."""
+    _dim_field = "robot_joint_dim"
+
+
+class GripperStatePredictor(_Mlp4Predictor):
+    """Predicts the change of the end effector's pose / gripper state (dynamics.py:305-338)."""
+    _dim_field = "robot_dim"
+
+
+class RobotModels(nn.Module):
+    """Both predictors in ONE flat parameter buffer (joint block, then the gripper block at the next 16-byte boundary) and
+    one gradient buffer: what optim.make_optimizer steps in a single launch.  `parameters()` is
+    `list(joint.parameters()) + list(gripper.parameters())`, the reference's optimiser order."""
+
+    def __init__(self, joint_model: JointPosPredictor, gripper_model: GripperStatePredictor):
+        super().__init__()
+        self.joint_model, self.gripper_model = joint_model, gripper_model
+        self._flatten()
+
+    def _flatten(self):
+        j, g = self.joint_model, self.gripper_model
+        dev = next(j.parameters()).device
+        if next(g.parameters()).device != dev:
+            raise ValueError("RobotModels: both models must live on one device")
+        self._gripper_off = (j.numel() + 3) // 4 * 4
+        total = (self._gripper_off + g.numel() + 3) // 4 * 4
+        self._flat = torch.zeros(total, device=dev, dtype=torch.float32)
+        self._flat_grad = torch.zeros_like(self._flat)
+        j._flatten(self._flat, self._flat_grad, 0)
+        g._flatten(self._flat, self._flat_grad, self._gripper_off)
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        self._flatten()
+        return out
+
+    def flat_parameters(self):
+        for m in (self.joint_model, self.gripper_model):
+            if m._root[0] is not self._flat:  # a model moved on its own (.to()) since: re-join the two
+                self._flatten()
+                break
+        return self._flat, self._flat_grad
+
+    def zero_grad(self, set_to_none: bool = False):
+        self.flat_parameters()[1].zero_()
+
+
+def resize_masks(rendered, height: int, width: int) -> np.ndarray:
+    """The video trainer's `_img_transform` (trainer.py:87-88: ToTensor, then Resize((image_height, image_width))) and the
+    `.type(torch.bool)` behind it (trainer.py:222-226), for a list of (H, W) renders of one shape: (n, height, width)
+    bool.  uint8 renders are scaled by 1 / 255 as ToTensor does; the resize is the bilinear one without antialiasing of
+    the reference's torchvision on tensors (and of this package's data path, data._resize), so a target pixel is set
+    where any of its four taps is; renders that already have the target shape pass through unchanged."""
+    arr = np.stack([np.asarray(m) for m in rendered])
+    if arr.ndim != 3:
+        raise ValueError(f"generate_masks must return (H, W) arrays, got {arr.shape[1:]}")
+    t = torch.from_numpy(np.ascontiguousarray(arr))
+    t = t.to(torch.float32) / 255 if t.dtype == torch.uint8 else t.to(torch.float32)
+    if tuple(t.shape[-2:]) != (height, width):
+        t = F.interpolate(t.unsqueeze(1), size=(height, width), mode="bilinear", align_corners=False).squeeze(1)
+    return (t != 0).numpy()
+
+
+class LearnedRobotModel:
+    """`PredictionTrainer.robot_model` over the two learned predictors.  `renderers`: {viewpoint: object with the reference
+    mask envs' `generate_masks(list_of_qpos) -> list of (H, W) arrays`}, looked up by `batch["folder"]`."""
+
+    def __init__(self, config, joint_model, gripper_model, renderers=None):
+        self._config = config
+        self.joint_model, self.gripper_model = joint_model, gripper_model
+        self.renderers = dict(renderers or {})
+
+    def rollout(self, qpos0, state0, actions):
+        """qpos[t+1] = qpos[t] + joint(qpos[t], a[t]) and states[t+1] = states[t] + gripper(states[t], a[t]) for the T
+        steps of actions (T, N, A), in one launch: (qpos (T+1, N, J), states (T+1, N, R)).  T = 0 launches nothing."""
+        jp, gp = self.joint_model.flat_parameters()[0], self.gripper_model.flat_parameters()[0]
+        if not (jp.is_cuda and gp.is_cuda):
+            raise _lib.RacError("LearnedRobotModel runs on the GPU only (no CPU fallback)")
+        dev = jp.device
+        qpos0 = torch.as_tensor(qpos0).to(dev, torch.float32)
+        state0 = torch.as_tensor(state0).to(dev, torch.float32)
+        actions = torch.as_tensor(actions).to(dev, torch.float32)
+        if actions.shape[0] == 0:
+            return qpos0.unsqueeze(0).clone(), state0.unsqueeze(0).clone()
+        if actions.shape[-1] != self.joint_model.action_dim or actions.shape[-1] != self.gripper_model.action_dim:
+            raise ValueError(f"actions of width {actions.shape[-1]}, the models take {self.joint_model.action_dim}")
+        return ops.robot_rollout(jp, gp, qpos0, state0, actions)
+
+    def _renderer(self, viewpoint):
+        env = self.renderers.get(viewpoint)
+        if env is not None:
+            return env
+        exp = getattr(self._config, "experiment", None)
+        try:  # the reference's MuJoCo mask envs (trainer.py:183-203): only inside a full reference checkout
+            from src.utils.camera_calibration import camera_to_world_dict
+            if exp == "finetune":
+                from src.env.robotics.masks.baxter_mask_env import BaxterMaskEnv
+                env = BaxterMaskEnv()
+                env.arm = "left"
+                cam_ext = camera_to_world_dict[f"baxter_{viewpoint}"]
+            elif exp == "finetune_widowx":
+                from src.env.robotics.masks.widowx_mask_env import WidowXMaskEnv
+                env = WidowXMaskEnv()
+                cam_ext = camera_to_world_dict[f"widowx_{viewpoint}"]
+            elif exp == "finetune_sawyer_view":
+                from src.env.robotics.masks.sawyer_mask_env import SawyerMaskEnv
+                env = SawyerMaskEnv()
+                cam_ext = camera_to_world_dict[f"sawyer_{viewpoint}"]
+            else:
+                raise ValueError(exp)
+            env.set_opencv_camera_pose("main_cam", cam_ext)
+        except Exception as e:
+            raise NotImplementedError(
+                f"no mask renderer for viewpoint {viewpoint!r}: pass renderers={{viewpoint: env}} to LearnedRobotModel, "
+                f"env being any object with generate_masks(list_of_qpos) -> list of (H, W) arrays.  The reference's "
+                f"MuJoCo mask envs (src.env.robotics.masks.*, experiment {exp!r}) exist only inside a full reference "
+                f"checkout and could not be imported here ({type(e).__name__}: {e})") from e
+        self.renderers[viewpoint] = env
+        return env
+
+    @torch.no_grad()
+    def predict_batch(self, batch):
+        """The reference's `_generate_learned_robot_states` (trainer.py:164-257): (states, masks) shaped like the batch's,
+        row 0 the ground truth, rows 1..T the models' rollout from row 0 over the window's actions (`raw_actions` when
+        `preprocess_action != "raw"`) and the render of every predicted joint position from its sample's viewpoint."""
+        cf = self._config
+        if getattr(cf, "model_use_heatmap", False):
+            raise NotImplementedError("model_use_heatmap with the learned robot model: the reference rebuilds the heatmaps "
+                                      "from the predicted states (create_heatmaps, trainer.py:234-256), which is not built")
+        states, mask, qpos = batch["states"], batch["masks"], batch["qpos"]
+        ac = batch["actions"] if getattr(cf, "preprocess_action", "raw") == "raw" else batch["raw_actions"]
+        folders = list(batch["folder"])
+        envs = {v: self._renderer(v) for v in dict.fromkeys(folders)}
+        q, s = self.rollout(qpos[0], states[0], ac)
+        T, B = q.shape[0] - 1, q.shape[1]
+        dev = q.device
+        pred_states = torch.zeros(tuple(states.shape), device=dev, dtype=torch.float32)
+        pred_states[:T + 1] = s
+        pred_masks = torch.zeros(tuple(mask.shape), device=dev, dtype=mask.dtype)
+        pred_masks[0] = torch.as_tensor(mask[0]).to(dev)
+        if T:
+            q_host = q[1:].cpu().numpy()  # the one device-to-host copy of the window
+            h, w = int(cf.image_height), int(cf.image_width)
+            if (h, w) != tuple(mask.shape[-2:]):
+                raise ValueError(f"image_height x image_width is {h} x {w}, the batch's masks are {tuple(mask.shape[-2:])}")
+            host = np.zeros((T, B) + tuple(mask.shape[2:]), dtype=np.bool_)
+            for b, vp in enumerate(folders):
+                rendered = envs[vp].generate_masks([q_host[t, b] for t in range(T)])
+                host[:, b, 0] = resize_masks(rendered, h, w)
+            pred_masks[1:T + 1] = torch.from_numpy(host).to(dev).to(mask.dtype)  # the one upload
+        return pred_states, pred_masks

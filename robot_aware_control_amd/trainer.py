@@ -172,6 +172,23 @@ class PredictionTrainer(object):
             dist.broadcast(self.model.flat_parameters()[0], src=0)
         # --optimizer adam | rmsprop | sgd (trainer.py:109-122); anything else is the reference's ValueError
         self.optimizer = make_optimizer(cf, self.model, bool(getattr(cf, "ddp_shard_optimizer", False) and _dist_on()))
+        if ("finetune" in cf.experiment and cf.experiment != "finetune_locobot"
+                and getattr(cf, "learned_robot_model", False)):
+            # --learned_robot_model True: states and masks of the finetune windows from the learned MLPs (trainer.py:123-130)
+            from .robot_model import GripperStatePredictor, JointPosPredictor, LearnedRobotModel
+            self.joint_model = JointPosPredictor(cf).to(self._device)
+            self.gripper_model = GripperStatePredictor(cf).to(self._device)
+            self._load_robot_model_checkpoint(getattr(cf, "robot_model_ckpt", None))
+            self.robot_model = LearnedRobotModel(cf, self.joint_model, self.gripper_model)
+
+    def _load_robot_model_checkpoint(self, ckpt_path):
+        """The two predictors of a RobotPredictionTrainer checkpoint (trainer.py:839-844)."""
+        if not ckpt_path or not os.path.exists(ckpt_path):
+            raise ValueError(f"--learned_robot_model True needs --robot_model_ckpt, a checkpoint written by "
+                             f"RobotPredictionTrainer (keys joint_model, gripper_model); got {ckpt_path!r}")
+        ckpt = torch.load(ckpt_path, map_location=self._device)
+        self.joint_model.load_state_dict(ckpt["joint_model"])
+        self.gripper_model.load_state_dict(ckpt["gripper_model"])
 
     def _schedule_prob(self):
         """Probability of feeding ground truth (trainer.py:132-140)."""
@@ -464,6 +481,8 @@ class PredictionTrainer(object):
                 for k in ("qpos",):
                     if k in data:
                         batch[k] = data[k][s:e]
+                if "folder" in data:  # the learned robot model renders each sample from its own viewpoint
+                    batch["folder"] = data["folder"]
                 if getattr(cf, "preprocess_action", "raw") != "raw":
                     batch["raw_actions"], batch["raw_states"] = data["raw_actions"][s:e - 1], data["raw_states"][s:e]
                     batch["raw_low"], batch["raw_high"] = data["raw_low"], data["raw_high"]
