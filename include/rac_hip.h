@@ -525,7 +525,8 @@ int rac_copy_baseline(const float* image, const float* next_image, const float* 
 
 /* Reconstruction losses + logging metrics in one pass (losses.py:11-78, trainer.py:149-161,426-452).
  * kind: 0 mse, 1 l1, 2 dontcare_mse, 3 dontcare_l1.  out[0] = loss, out[1] = robot_mse, out[2] = world_mse
- * (out[1..2] only when mask != NULL).  per_sample = workspace fp32 [B][8]. */
+ * (out[1..2] only when mask != NULL; 0 without one).  batch_weight [B] or NULL weighs the samples of the two l1 kinds, as
+ * the reference's criteria do; mse and dontcare_mse take none and ignore it.  per_sample = workspace fp32 [B][8]. */
 enum { RAC_LOSS_MSE = 0, RAC_LOSS_L1 = 1, RAC_LOSS_DONTCARE_MSE = 2, RAC_LOSS_DONTCARE_L1 = 3 };
 int rac_recon_loss_fwd(int32_t kind, const float* pred, const float* target, const float* mask, float robot_weight,
                        const float* batch_weight, float* per_sample, float* out, int32_t B, int32_t HW, void* stream);

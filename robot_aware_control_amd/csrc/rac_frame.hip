@@ -408,13 +408,12 @@ __global__ void recon_loss_final_kernel(int kind, const float* per_sample, const
   float a = 0.f, r = 0.f, w = 0.f;
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
     const float* s = per_sample + b * 8;
-    float wt = bw ? bw[b] : 1.f;
+    // batch_weight belongs to the two l1 losses alone (losses.py:13-19, 35-50): mse and dontcare_mse take none
+    float wt = (bw && (kind == RAC_LOSS_L1 || kind == RAC_LOSS_DONTCARE_L1)) ? bw[b] : 1.f;
     if (kind == RAC_LOSS_DONTCARE_L1 || kind == RAC_LOSS_DONTCARE_MSE)
       a += wt * s[0] / (s[1] + 1.f);
-    else if (kind == RAC_LOSS_L1)
-      a += wt * (s[0] / (3.f * HW));
     else
-      a += s[0] / (3.f * HW);
+      a += wt * (s[0] / (3.f * HW));
     if (has_mask) {
       r += s[2] / (s[3] + 1.f);
       w += s[4] / (s[1] + 1.f);
@@ -438,7 +437,7 @@ __global__ void recon_loss_bwd_kernel(int kind, const float* pred, const float* 
     int p = (int)(i - bc * HW);
     int b = (int)(bc / 3);
     float d = target[i] - pred[i];
-    float wt = bw ? bw[b] : 1.f;
+    float wt = (bw && (kind == RAC_LOSS_L1 || kind == RAC_LOSS_DONTCARE_L1)) ? bw[b] : 1.f;
     float coef, dm = d, inner = 1.f;
     if (kind == RAC_LOSS_DONTCARE_L1 || kind == RAC_LOSS_DONTCARE_MSE) {
       coef = wt / ((per_sample[b * 8 + 1] + 1.f) * B);
@@ -447,7 +446,7 @@ __global__ void recon_loss_bwd_kernel(int kind, const float* pred, const float* 
         inner = rw;
       }
     } else {
-      coef = ((kind == RAC_LOSS_L1) ? wt : 1.f) / (3.f * HW * B);
+      coef = wt / (3.f * HW * B);
     }
     float dd;  // d loss_elem / d dm
     if (kind == RAC_LOSS_L1 || kind == RAC_LOSS_DONTCARE_L1)
@@ -934,17 +933,17 @@ extern "C" int rac_psnr_ssim(const float* a, const float* b, const float* mask, 
   using namespace rac;
   RAC_REQUIRE(a && b && sq_err && ssim_sum && N > 0 && H > 0 && W > 0, "rac_psnr_ssim: bad args");
   SsimWin win;
+  // gaussian(11, 1.5) of src/utils/metrics.py:13-15: fp32 values over their fp32 sum.  The sum is the correctly rounded one
+  // (3.7592328, what torch's gauss.sum() gives); adding the eleven floats one after another in fp32 ends one ulp lower
+  // (3.7592325), which makes nine of the weights one ulp larger and the window's total 1 + 8e-8 instead of 1 - 7e-8: a bias
+  // of the same sign in every pixel's SSIM, 7e-6 of the per-sample sum at 64 x 64.
+  float gf[11];
   double tot = 0.0;
-  double gd[11];
-  for (int i = 0; i < 11; ++i) {  // gaussian(11, 1.5) of src/utils/metrics.py:13-15, normalised in fp32 like torch
-    gd[i] = exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
-  }
-  float gf[11], sum = 0.f;
   for (int i = 0; i < 11; ++i) {
-    gf[i] = (float)gd[i];
-    sum += gf[i];
+    gf[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
+    tot += (double)gf[i];
   }
-  (void)tot;
+  const float sum = (float)tot;
   for (int i = 0; i < 11; ++i) win.g[i] = gf[i] / sum;
   const int tx = cdiv(W, SS_T), ty = cdiv(H, SS_T);
   hipLaunchKernelGGL(psnr_ssim_kernel, dim3(tx * ty, 3, N), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, b,
