@@ -679,6 +679,36 @@ int rac_mlp4_bwd(const float* params, const float* x, const float* a, const floa
  * a fixed summation order (joint_pos_trainer.py:173-211 with its steps batched as rows: scale = 1 / (B D)). */
 int rac_mse_rows(const float* pred, const float* target, float scale, float* loss, float* dy, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * The learned robot model's data path (src/dataset/joint_pos_dataset.py) and mask plot (joint_pos_trainer.py:467-567).
+ * ------------------------------------------------------------------------ */
+/* One training batch from a split that lives on the device in STORED form, in one launch:
+ *   states[N][Tmax][R] fp64 (fp32 files widened), actions[N][Tmax-1][A] fp32 (a file of width A - 1 fills its first
+ *   A - 1 columns), qpos[N][Tmax][J] fp32, bounds[N][2][R] fp64 (low, high; fp32 files widened),
+ *   meta[N][3] = {episode length, the file's action width (A or A - 1), 1 when the bounds are stored as float64}.
+ * index[B] / start[B] (device memory) name each sample's trajectory and window start; the window is L steps.  Outputs,
+ * time-first: qpos_out[L][B][J], states_out[L][B][R], actions_out[L-1][B][A], with the dataset's preprocessing in the
+ * host's precision and floating-point contraction off:
+ *   - a missing last action column is the imputed gripper command: high[R-1] where the next stored state's last column
+ *     is above (high[R-1] + low[R-1]) / 2, else low[R-1];
+ *   - state_infer != 0: action columns 0..2 are the difference of the next and the current state's xyz, each
+ *     denormalised as  s * (high - low) + low  -- in fp64 rounded once to fp32 when the bounds are stored as float64,
+ *     in fp32 otherwise;
+ *   - states column 4 is (s - low[4]) / (high[4] - low[4]) in fp32.
+ * The same bits as the host dataset -> collate -> process_batch.  The entry point cannot see index / start: the caller
+ * checks them (0 <= index < N, 0 <= start <= length - L) before the upload, and the kernel clamps both so that no value
+ * reads outside the resident arrays.  2 <= L <= Tmax, R >= 5, A >= 3 with state_infer. */
+int rac_joint_batch(const double* states, const float* actions, const float* qpos, const double* bounds,
+                    const int32_t* meta, const int32_t* index, const int32_t* start, float* qpos_out, float* states_out,
+                    float* actions_out, int32_t N, int32_t Tmax, int32_t B, int32_t L, int32_t J, int32_t R, int32_t A,
+                    int32_t state_infer, void* stream);
+/* Predicted against true masks, pred / truth [V][T][H][W] fp32 (set where nonzero), one workgroup per frame:
+ *   counts[V][T][2] = {|pred & true|, |pred | true|}, exact int32, a fixed-order reduction;
+ *   frames[T][V H][3 W] uint8 = per video one row [true | predicted | xor]: the two masks clamped to [0, 1] times 255
+ *   (truncated), the xor 0 or 255. */
+int rac_mask_compare(const float* pred, const float* truth, int32_t* counts, uint8_t* frames, int32_t V, int32_t T,
+                     int32_t H, int32_t W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

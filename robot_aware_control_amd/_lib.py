@@ -180,6 +180,8 @@ _SIGS = {
     "rac_robot_rollout": [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, i32, vp],
     "rac_mlp4_bwd": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
     "rac_mse_rows": [vp, vp, f32, vp, vp, i64, vp],
+    "rac_joint_batch": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "rac_mask_compare": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "rac_version": [],
     "rac_device_arch": [],
     "rac_last_error": [],

@@ -3334,6 +3334,49 @@ def mse_rows(pred, target, scale, loss=None, want_grad=False):
     return loss, dy
 
 
+def joint_batch(states, actions, qpos, bounds, meta, index, start, window, state_infer):
+    """One batch of the device-resident joint-position split (joint_pos_data.DeviceJointPosData; include/rac_hip.h
+    rac_joint_batch): time-first (qpos (L, B, J), states (L, B, R), actions (L - 1, B, A)) of the windows
+    [start_b, start_b + L) of the trajectories index_b.  `index` / `start` are int32 device tensors the CALLER has checked
+    against the episode lengths (DeviceJointPosData.check): the entry point cannot read them."""
+    for t, dtype, dim in ((states, torch.float64, 3), (actions, torch.float32, 3), (qpos, torch.float32, 3),
+                          (bounds, torch.float64, 3), (meta, torch.int32, 2), (index, torch.int32, 1),
+                          (start, torch.int32, 1)):
+        _require_cuda(t)
+        if t.dtype != dtype or t.dim() != dim or not t.is_contiguous():
+            raise ValueError(f"joint_batch: expected a contiguous {dtype} tensor of {dim} dims, got {t.dtype} {tuple(t.shape)}")
+    N, Tmax, R = states.shape
+    J, A, B, L = qpos.shape[2], actions.shape[2], index.shape[0], int(window)
+    if (tuple(actions.shape[:2]) != (N, Tmax - 1) or tuple(qpos.shape[:2]) != (N, Tmax) or tuple(bounds.shape) != (N, 2, R)
+            or tuple(meta.shape) != (N, 3) or start.shape[0] != B or B < 1):
+        raise ValueError(f"joint_batch: states {tuple(states.shape)}, actions {tuple(actions.shape)}, qpos "
+                         f"{tuple(qpos.shape)}, bounds {tuple(bounds.shape)}, meta {tuple(meta.shape)}, {B} / "
+                         f"{start.shape[0]} samples do not belong together")
+    dev = states.device
+    q = torch.empty((L, B, J), device=dev, dtype=torch.float32)
+    s = torch.empty((L, B, R), device=dev, dtype=torch.float32)
+    a = torch.empty((L - 1, B, A), device=dev, dtype=torch.float32)
+    call("rac_joint_batch", ptr(states), ptr(actions), ptr(qpos), ptr(bounds), ptr(meta), ptr(index), ptr(start), ptr(q),
+         ptr(s), ptr(a), N, Tmax, B, L, J, R, A, int(bool(state_infer)), stream_ptr())
+    return q, s, a
+
+
+def mask_compare(pred, truth):
+    """Predicted against true masks (V, T, H, W) float32 in one launch: (counts (V, T, 2) int32 of |pred & true| and
+    |pred | true| per frame, frames (T, V H, 3 W) uint8 with one row [true | predicted | xor] per video)."""
+    _require_cuda(pred)
+    _require_cuda(truth)
+    if pred.shape != truth.shape or pred.dim() != 4 or pred.dtype != torch.float32 or truth.dtype != torch.float32:
+        raise ValueError(f"mask_compare: two float32 (V, T, H, W) tensors, got {pred.dtype} {tuple(pred.shape)} and "
+                         f"{truth.dtype} {tuple(truth.shape)}")
+    pred, truth = pred.contiguous(), truth.contiguous()
+    V, T, H, W = pred.shape
+    counts = torch.empty((V, T, 2), device=pred.device, dtype=torch.int32)
+    frames = torch.empty((T, V * H, 3 * W), device=pred.device, dtype=torch.uint8)
+    call("rac_mask_compare", ptr(pred), ptr(truth), ptr(counts), ptr(frames), V, T, H, W, stream_ptr())
+    return counts, frames
+
+
 class Mlp4(torch.autograd.Function):
     """delta = MLP([x | a]) of one predictor (dynamics.py:290-302, :326-338).  `anchor` is one of the model's parameters: it
     carries requires_grad into the tape; the parameter gradients are accumulated into the model's gradient block by the

@@ -168,6 +168,41 @@ def resize_masks(rendered, height: int, width: int) -> np.ndarray:
     return (t != 0).numpy()
 
 
+def mask_renderer(renderers, config, viewpoint):
+    """`renderers[viewpoint]`, built on first use from the reference's MuJoCo mask envs (trainer.py:183-203,
+    joint_pos_trainer.py:481-500) where those import; shared by LearnedRobotModel and RobotPredictionTrainer.plot."""
+    env = renderers.get(viewpoint)
+    if env is not None:
+        return env
+    exp = getattr(config, "experiment", None)
+    try:  # the reference's MuJoCo mask envs: only inside a full reference checkout
+        from src.utils.camera_calibration import camera_to_world_dict
+        if exp in ("finetune", "finetune_baxter"):
+            from src.env.robotics.masks.baxter_mask_env import BaxterMaskEnv
+            env = BaxterMaskEnv()
+            env.arm = "left"
+            cam_ext = camera_to_world_dict[f"baxter_{viewpoint}"]
+        elif exp == "finetune_widowx":
+            from src.env.robotics.masks.widowx_mask_env import WidowXMaskEnv
+            env = WidowXMaskEnv()
+            cam_ext = camera_to_world_dict[f"widowx_{viewpoint}"]
+        elif exp == "finetune_sawyer_view":
+            from src.env.robotics.masks.sawyer_mask_env import SawyerMaskEnv
+            env = SawyerMaskEnv()
+            cam_ext = camera_to_world_dict[f"sawyer_{viewpoint}"]
+        else:
+            raise ValueError(exp)
+        env.set_opencv_camera_pose("main_cam", cam_ext)
+    except Exception as e:
+        raise NotImplementedError(
+            f"no mask renderer for viewpoint {viewpoint!r}: pass renderers={{viewpoint: env}} to LearnedRobotModel, "
+            f"env being any object with generate_masks(list_of_qpos) -> list of (H, W) arrays.  The reference's "
+            f"MuJoCo mask envs (src.env.robotics.masks.*, experiment {exp!r}) exist only inside a full reference "
+            f"checkout and could not be imported here ({type(e).__name__}: {e})") from e
+    renderers[viewpoint] = env
+    return env
+
+
 class LearnedRobotModel:
     """`PredictionTrainer.robot_model` over the two learned predictors.  `renderers`: {viewpoint: object with the reference
     mask envs' `generate_masks(list_of_qpos) -> list of (H, W) arrays`}, looked up by `batch["folder"]`."""
@@ -194,36 +229,7 @@ class LearnedRobotModel:
         return ops.robot_rollout(jp, gp, qpos0, state0, actions)
 
     def _renderer(self, viewpoint):
-        env = self.renderers.get(viewpoint)
-        if env is not None:
-            return env
-        exp = getattr(self._config, "experiment", None)
-        try:  # the reference's MuJoCo mask envs (trainer.py:183-203): only inside a full reference checkout
-            from src.utils.camera_calibration import camera_to_world_dict
-            if exp == "finetune":
-                from src.env.robotics.masks.baxter_mask_env import BaxterMaskEnv
-                env = BaxterMaskEnv()
-                env.arm = "left"
-                cam_ext = camera_to_world_dict[f"baxter_{viewpoint}"]
-            elif exp == "finetune_widowx":
-                from src.env.robotics.masks.widowx_mask_env import WidowXMaskEnv
-                env = WidowXMaskEnv()
-                cam_ext = camera_to_world_dict[f"widowx_{viewpoint}"]
-            elif exp == "finetune_sawyer_view":
-                from src.env.robotics.masks.sawyer_mask_env import SawyerMaskEnv
-                env = SawyerMaskEnv()
-                cam_ext = camera_to_world_dict[f"sawyer_{viewpoint}"]
-            else:
-                raise ValueError(exp)
-            env.set_opencv_camera_pose("main_cam", cam_ext)
-        except Exception as e:
-            raise NotImplementedError(
-                f"no mask renderer for viewpoint {viewpoint!r}: pass renderers={{viewpoint: env}} to LearnedRobotModel, "
-                f"env being any object with generate_masks(list_of_qpos) -> list of (H, W) arrays.  The reference's "
-                f"MuJoCo mask envs (src.env.robotics.masks.*, experiment {exp!r}) exist only inside a full reference "
-                f"checkout and could not be imported here ({type(e).__name__}: {e})") from e
-        self.renderers[viewpoint] = env
-        return env
+        return mask_renderer(self.renderers, self._config, viewpoint)
 
     @torch.no_grad()
     def predict_batch(self, batch):

@@ -10,7 +10,10 @@ the rollout kernel (one launch for both models and all steps).
 Differences from the reference, all on purpose:
   * `*_joint_eef_pos_loss` (forward kinematics of predicted vs. input joints, MuJoCo) is computed only when the trainer
     has a `forward_kinematics(qpos) -> xyz` callable, and the key is omitted otherwise;
-  * `plot` (mask GIFs and IoU) is not built: `train` skips it;
+  * the batches come from the device-resident split (joint_pos_data.DeviceBatches: one gather launch per batch, the host
+    loader's order and bits), not from a DataLoader; the host dataset and loaders remain for `plot`'s true masks;
+  * `plot` (mask GIFs and IoU) runs under `--plot True` only, needs `renderers` (the reference's MuJoCo mask envs where
+    they import) and compares the masks in one `rac_mask_compare` launch;
   * loaders can be injected into `train`, in `PredictionTrainer.train`'s style.
 Checkpoints are the reference's (`joint_model`, `gripper_model`, `optimizer`, `step`) and load in both directions.
 """
@@ -25,14 +28,16 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .joint_pos_data import DeviceBatches, mask_iou, mask_transform
 from .optim import make_optimizer
-from .robot_model import GripperStatePredictor, JointPosPredictor, RobotModels
+from .robot_model import GripperStatePredictor, JointPosPredictor, RobotModels, mask_renderer
 
 FINETUNE_EXPERIMENTS = ("finetune", "finetune_sawyer_view", "finetune_widowx")  # joint_pos_trainer.py:427
 
 
 class RobotPredictionTrainer(object):
-    def __init__(self, config, logger=None, forward_kinematics=None):
+    def __init__(self, config, logger=None, forward_kinematics=None, renderers=None):
+        """`renderers`: {viewpoint: object with the reference mask envs' `generate_masks(list_of_qpos)`}, for `plot`."""
         self._config = config
         if not torch.cuda.is_available():
             raise _lib.RacError("RobotPredictionTrainer needs an MI355X (no CPU fallback)")
@@ -44,6 +49,9 @@ class RobotPredictionTrainer(object):
         self._init_models(config)
         self._scheduled_sampling = getattr(config, "scheduled_sampling", False)
         self._step = 0
+        self.renderers = dict(renderers or {})
+        self._plot_rng = np.random.RandomState(getattr(config, "seed", 0))
+        self.train_loader = self.test_loader = self.training_batch_generator = self.testing_batch_generator = None
         self._wandb = None
         if getattr(config, "wandb", False):
             import wandb  # only when asked for (joint_pos_trainer.py:53-66)
@@ -179,24 +187,50 @@ class RobotPredictionTrainer(object):
             self._logger.info(", ".join(f"{k}: {v:.5f}" for k, v in avg.items()))
         return avg
 
+    def _setup_data(self):
+        """joint_pos_trainer.py:434-447: the experiment's host loaders, and both batch generators from the device-resident
+        splits.  `test_batches` is the test split's one-epoch form, what `_compute_epoch_metrics` walks."""
+        cf = self._config
+        if cf.experiment == "finetune_baxter":
+            from .joint_pos_data import create_finetune_loaders as create_loaders
+        elif cf.experiment == "finetune_widowx":
+            from .joint_pos_data import create_loaders
+        else:
+            raise NotImplementedError(cf.experiment)
+        self.train_loader, self.test_loader = create_loaders(cf)
+        self.train_batches = DeviceBatches(self.train_loader, self._device)
+        self.test_batches = DeviceBatches(self.test_loader, self._device)
+        self.training_batch_generator = self.train_batches.forever()
+        self.testing_batch_generator = self.test_batches.forever()
+
     def train(self, batch_generator=None, test_loader=None):
-        """Training, evaluation and checkpoint loop (joint_pos_trainer.py:327-368; no plots).  `batch_generator` yields
-        time-first batches (qpos (T, B, J), states (T, B, R), actions (T - 1, B, A)); `test_loader` yields batch-first ones."""
+        """Training, evaluation and checkpoint loop (joint_pos_trainer.py:327-368).  Without arguments the data are the
+        experiment's (`_setup_data`).  An injected `batch_generator` yields time-first batches (qpos (T, B, J), states
+        (T, B, R), actions (T - 1, B, A)); an injected `test_loader` yields batch-first ones; that form never plots.  On the
+        experiment's own data `--plot True` writes the mask GIF and IoU where the reference writes them: on an epoch's
+        last batch and after each evaluation."""
         cf = self._config
         self._step = self._load_checkpoint(getattr(cf, "dynamics_model_ckpt", None))
+        test_generator = None
         if batch_generator is None:
-            raise NotImplementedError(
-                "RobotPredictionTrainer.train: pass batch_generator (and test_loader); the reference's joint-position "
-                "dataloaders (src/dataset/*/..._joint_pos_dataloaders.py) are not built")
+            self._setup_data()
+            batch_generator, test_generator = self.training_batch_generator, self.testing_batch_generator
+            if test_loader is None:
+                test_loader = self.test_batches
+        plot = bool(getattr(cf, "plot", False)) and test_generator is not None  # injected batches: no plot, as before
         info = {}
         self.eval_history = []
+        self.plot_history = []
         for epoch in range(cf.niter):
             self.models.train()
-            for _ in range(cf.epoch_size):
-                info = dict(self._train_video(next(batch_generator)))
+            for i in range(cf.epoch_size):
+                data = next(batch_generator)
+                info = dict(self._train_video(data))
                 if self._scheduled_sampling:
                     info["sample_schedule"] = self._schedule_prob()[0]
                 self._step += 1
+                if plot and i == cf.epoch_size - 1:
+                    self.plot_history.append(self.plot(data, epoch, "train"))
                 if self._wandb is not None:
                     self._wandb.log({f"train/{k}": v for k, v in info.items()}, step=self._step)
             if epoch % cf.checkpoint_interval == 0 and epoch > 0:
@@ -207,7 +241,66 @@ class RobotPredictionTrainer(object):
                 self.eval_history.append((epoch, metrics))
                 if self._wandb is not None:
                     self._wandb.log(metrics, step=self._step)
+                if plot:
+                    self.plot_history.append(self.plot(next(test_generator), epoch, "test"))
         return info
+
+    # ------------------------------------------------------------------ plot
+    def _true_masks(self, data, name, b, start, length):
+        """(b, length, w, w) true masks of the plotted window: the batch's own where it carries them (a host loader's
+        batch), else the host dataset's by `idx` -- the device batches carry none."""
+        if "masks" in data:
+            return data["masks"][start:start + length, :b, 0].transpose(0, 1).to("cpu", torch.float32)
+        loader = self.train_loader if name in ("comparison", "train") else self.test_loader
+        if loader is None or "idx" not in data or "start" not in data:
+            raise ValueError("plot: the batch has no masks and no (idx, start) of a host dataset to read them from")
+        ds = loader.dataset
+        return torch.stack([ds.masks(int(i), int(s) + start, length)[:, 0]
+                            for i, s in zip(list(data["idx"])[:b], list(data["start"])[:b])])
+
+    @torch.no_grad()
+    def plot(self, data, epoch, name, random_start=True):
+        """joint_pos_trainer.py:467-567: the joint model's autoregressive rollout of up to 10 videos, rendered to masks and
+        compared with the true ones.  One rollout launch, one device-to-host copy of the joint positions, one
+        `generate_masks` call per video, one upload of both mask stacks and one `rac_mask_compare` launch for the IoU
+        counts and the GIF's frames (per video one row [true | predicted | xor], one GIF frame per time step).
+        `data`: a time-first batch.  Returns {"file": <plot_dir>/<name>_<epoch>.gif, "IoU": mean IoU}."""
+        from PIL import Image
+        cf = self._config
+        dev, f32 = self._device, torch.float32
+        qpos, ac = torch.as_tensor(data["qpos"]).to(dev, f32), torch.as_tensor(data["actions"]).to(dev, f32)
+        b = min(qpos.shape[1], 10)
+        length = cf.n_past + cf.n_future if name in ("comparison", "train") else cf.n_eval
+        if qpos.shape[0] < length or ac.shape[0] < length - 1:
+            raise ValueError(f"plot: a window of {length} steps from a batch of {qpos.shape[0]}")
+        start = int(self._plot_rng.randint(0, qpos.shape[0] - length + 1)) if random_start else 0
+        folders = list(data["folder"])[:b]
+        envs = {v: mask_renderer(self.renderers, cf, v) for v in dict.fromkeys(folders)}
+        q0 = qpos[start, :b].contiguous()
+        if length > 1:
+            jp = self.joint_model.flat_parameters()[0]
+            q_all, _ = ops.robot_rollout(jp, None, q0, None, ac[start:start + length - 1, :b].contiguous())
+        else:
+            q_all = q0.unsqueeze(0)
+        q_host = q_all.cpu().numpy()  # the one device-to-host copy
+        size = int(cf.image_width)
+        pred = torch.stack([mask_transform(envs[vp].generate_masks([q_host[t, i] for t in range(length)]), size)[:, 0]
+                            for i, vp in enumerate(folders)])
+        true = self._true_masks(data, name, b, start, length)
+        if pred.shape != true.shape:
+            raise ValueError(f"plot: rendered masks {tuple(pred.shape)}, true masks {tuple(true.shape)}")
+        both = torch.stack([pred, true]).to(dev)  # the one upload
+        counts, frames = ops.mask_compare(both[0], both[1])
+        iou = mask_iou(counts.cpu())
+        imgs = [Image.fromarray(f) for f in frames.cpu().numpy()]
+        plot_dir = getattr(cf, "plot_dir", None) or os.path.join(cf.log_dir, "plot")
+        os.makedirs(plot_dir, exist_ok=True)
+        fname = os.path.join(plot_dir, f"{name}_{epoch}.gif")
+        imgs[0].save(fname, save_all=True, append_images=imgs[1:], duration=250, loop=0)
+        if self._wandb is not None:
+            self._wandb.log({f"{name}/gifs": self._wandb.Video(fname, format="gif")}, step=self._step)
+            self._wandb.log({f"{name}/IoU": iou}, step=self._step)
+        return {"file": fname, "IoU": iou}
 
     # ------------------------------------------------------------------ checkpoints
     def _save_checkpoint(self):
