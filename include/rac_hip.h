@@ -550,6 +550,22 @@ int rac_kl_bwd(const float* mu1, const float* lv1, const float* mu2, const float
 int rac_psnr_ssim(const float* a, const float* b, const float* mask, float* sq_err, float* ssim_sum, float* ssim_map,
                   int32_t N, int32_t H, int32_t W, void* stream);
 
+/* Everything `_eval_step` scores on one predicted frame (trainer.py:650-713: losses.py:11-78, src/utils/metrics.py:13-78),
+ * for S prior samples of B videos in one launch (the best-of-three of `_eval_video`, trainer.py:497-499, 552-560).
+ * pred [S*B][3][H][W], sample group s = rows [sB, (s+1)B); target [B][3][H][W] and mask [B][1][H][W] (or NULL: no robot
+ * pixel anywhere) are shared by the groups: video n = sB + b is scored against row b.  rows [S*B][8] fp32 is OVERWRITTEN
+ * with per-video sums that are not yet averaged over the batch:
+ *   rows[n][0] = sum |d'| (l1 kinds) or d'^2 (mse kinds), d = target - pred, d' = robot_weight * d on robot pixels for
+ *                the two dontcare kinds and d elsewhere (losses.py:21-50)
+ *   rows[n][1] = sum of d^2 over robot pixels, rows[n][2] = over world pixels (losses.py:52-78)
+ *   rows[n][3] = number of robot values (3 per masked pixel); the world count is 3HW minus it
+ *   rows[n][4] = sq_err of rac_psnr_ssim (frames blacked by mask, clamped to [0,1], difference halved)
+ *   rows[n][5..7] = ssim_sum of rac_psnr_ssim for channel 0, 1, 2 (same window, padding, C1 and C2)
+ * A row's bits depend only on that video's pred, target and mask and on (H, W): not on S, B, the row's position or
+ * the run (no atomics; every sum in one fixed order). */
+int rac_eval_frames(int32_t kind, const float* pred, const float* target, const float* mask, float robot_weight,
+                    float* rows, int32_t S, int32_t B, int32_t H, int32_t W, void* stream);
+
 /* CEM step tail (trajectory_sampler.py:149-169 + losses.py:224-263), fused:
  *   next = (1-m)*curr + m*rgb; next *= (1-next_mask) if next_mask;
  *   cost = -sqrt(sum (255*(next-goal))^2) [dontcare: robot|goal-mask pixels dropped, / #world pixels]

@@ -951,4 +951,189 @@ extern "C" int rac_psnr_ssim(const float* a, const float* b, const float* mask, 
   return check_launch("rac_psnr_ssim");
 }
 
+// ---- every metric of one predicted frame, every sample of every video, one launch ------------------------------
+namespace rac {
+
+constexpr int EV_THREADS = 1024;         // 16 waves, 4 per SIMD (the kernel needs 88 VGPRs)
+constexpr int EV_ROWS = 4;               // vertically adjacent outputs of one thread
+constexpr int EV_TH = (EV_THREADS / 64) * EV_ROWS;  // output super-tile: 64 rows (16 waves x 4) x 64 columns
+constexpr int EV_TW = 64;
+constexpr int EV_EH = EV_TH + 2 * SS_R, EV_EW = EV_TW + 2 * SS_R;  // staged incl. halo
+
+// Sum over the workgroup's 16 waves, wave 0 first: the xor butterfly inside a wave and the serial add across waves are
+// the same operations in the same order on every launch.  `sh` holds 16 floats; every thread gets the total.
+__device__ __forceinline__ float eval_block_sum(float v, float* sh) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = sh[0];
+#pragma unroll
+  for (int k = 1; k < EV_THREADS / 64; ++k) t += sh[k];
+  return t;
+}
+
+// grid 3 * S * B, 1024 threads: workgroup (n, c) owns channel plane c of video n = s B + b and nothing else of the row
+// but its own columns, so no value crosses a workgroup.  The plane is staged with its 5-pixel halo (zero outside the
+// image, robot pixels blacked) in super-tiles of 64 x 64 outputs -- one at 64 x 64 and at 48 x 64 -- and each thread slides
+// the 11 x 11 window down 4 vertically adjacent outputs, so that a staged value and its three products are formed once
+// for the up to 4 outputs they feed.  Per output the taps are added i-major, j-minor, as psnr_ssim_kernel adds them.
+// Workgroup c == 0 also makes the one streaming pass over all three channels for the loss, error and PSNR sums.
+// rows[n]: 0 loss numerator, 1 robot sum d^2, 2 world sum d^2, 3 #robot values, 4 PSNR squared error, 5..7 SSIM sum of
+// channel 0..2.
+__global__ void __launch_bounds__(EV_THREADS) eval_frames_kernel(int kind, const float* pred, const float* target,
+                                                            const float* mask, float rw, float* rows, int B, int H,
+                                                            int W, SsimWin win) {
+  __shared__ float sa[EV_EH][EV_EW], sb[EV_EH][EV_EW];
+  __shared__ float red[EV_THREADS / 64];
+  __shared__ float sg[11];  // the window's row weight, read at a wave-uniform index (visible after the staging barrier)
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < 11; ++i) sg[i] = win.g[i];
+  }
+  const int n = blockIdx.x / 3, c = blockIdx.x - n * 3;
+  const int b = n % B;
+  const long HW = (long)H * W;
+  const float* tp = target + ((long)b * 3 + c) * HW;  // a = target, b = pred, the order metrics.masked_psnr_ssim passes
+  const float* pp = pred + ((long)n * 3 + c) * HW;
+  const float* mp = mask ? mask + (long)b * HW : nullptr;
+  const int lx = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  float ss = 0.f;
+  for (int ty0 = 0; ty0 < H; ty0 += EV_TH) {
+    const int th = min(EV_TH, H - ty0);
+    const int staged_rows = ((th + EV_ROWS - 1) / EV_ROWS) * EV_ROWS + 2 * SS_R;  // <= EV_EH: what the live waves read
+    for (int tx0 = 0; tx0 < W; tx0 += EV_TW) {
+      __syncthreads();  // the previous super-tile has been read
+      for (int i = threadIdx.x; i < staged_rows * EV_EW; i += EV_THREADS) {
+        const int ly = i / EV_EW, sx = i - ly * EV_EW;
+        const int y = ty0 + ly - SS_R, x = tx0 + sx - SS_R;
+        float va = 0.f, vb = 0.f;
+        if ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) {
+          const long p = (long)y * W + x;
+          va = tp[p];
+          vb = pp[p];
+          if (mp && mp[p] != 0.f) {
+            va *= 0.f;
+            vb *= 0.f;
+          }
+        }
+        sa[ly][sx] = va;
+        sb[ly][sx] = vb;
+      }
+      __syncthreads();
+      const int ly0 = wv * EV_ROWS;
+      if (ly0 < th) {  // wave-uniform
+        float acc[EV_ROWS][5];
+#pragma unroll
+        for (int o = 0; o < EV_ROWS; ++o)
+#pragma unroll
+          for (int k = 0; k < 5; ++k) acc[o][k] = 0.f;
+        // One staged row per trip of a loop that stays a loop: unrolled over the rows too, every one of the 308 LDS
+        // reads and their 462 products is lifted above the arithmetic and lives in scratch (566 to 750 spilled VGPRs in
+        // every form tried).  Row r feeds output o through window row i = r - o, a wave-uniform test.
+#pragma unroll 1
+        for (int r = 0; r < EV_ROWS + 2 * SS_R; ++r) {
+          float p[11], q[11], p2[11], q2[11], pq[11];
+#pragma unroll
+          for (int j = 0; j < 11; ++j) {
+            p[j] = sa[ly0 + r][lx + j];
+            q[j] = sb[ly0 + r][lx + j];
+            p2[j] = p[j] * p[j];
+            q2[j] = q[j] * q[j];
+            pq[j] = p[j] * q[j];
+          }
+#pragma unroll
+          for (int o = 0; o < EV_ROWS; ++o) {
+            const int i = r - o;
+            if ((unsigned)i < 11u) {
+              const float gi = sg[i];
+#pragma unroll
+              for (int j = 0; j < 11; ++j) {
+                const float w = gi * win.g[j];
+                acc[o][0] += w * p[j];
+                acc[o][1] += w * q[j];
+                acc[o][2] += w * p2[j];
+                acc[o][3] += w * q2[j];
+                acc[o][4] += w * pq[j];
+              }
+            }
+          }
+        }
+        // an output past the image's edge sees staged zeros (SSIM 1) and is left out by a select, not a branch: a
+        // branch here lets the compiler sink each output's 605 fused multiply-adds into its own block, and the 770
+        // staged values and products they share then live in scratch
+        const bool col_in = tx0 + lx < W;
+#pragma unroll
+        for (int o = 0; o < EV_ROWS; ++o) {
+          const float m1 = acc[o][0], m2 = acc[o][1];
+          const float m1s = m1 * m1, m2s = m2 * m2, m12 = m1 * m2;
+          const float v1 = acc[o][2] - m1s, v2 = acc[o][3] - m2s, v12 = acc[o][4] - m12;
+          const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+          const float s = ((2.f * m12 + C1) * (2.f * v12 + C2)) / ((m1s + m2s + C1) * (v1 + v2 + C2));
+          ss += (col_in && ly0 + o < th) ? s : 0.f;
+        }
+      }
+    }
+  }
+  const float ssim = eval_block_sum(ss, red);
+  float* o = rows + (long)n * 8;
+  if (c != 0) {
+    if (threadIdx.x == 0) o[5 + c] = ssim;
+    return;
+  }
+  // the streaming pass: the sums of recon_loss_sample_kernel and the squared error of psnr_ssim_kernel
+  float s_main = 0.f, s_rob2 = 0.f, s_world2 = 0.f, s_rob_n = 0.f, s_se = 0.f;
+  const float* t3 = target + (long)b * 3 * HW;
+  const float* p3 = pred + (long)n * 3 * HW;
+  const bool weighted = kind == RAC_LOSS_DONTCARE_L1 || kind == RAC_LOSS_DONTCARE_MSE;
+  const bool l1 = kind == RAC_LOSS_L1 || kind == RAC_LOSS_DONTCARE_L1;
+  for (long p = threadIdx.x; p < HW; p += EV_THREADS) {
+    const bool rob = mp && mp[p] != 0.f;
+    if (rob) s_rob_n += 3.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      float tv = t3[ch * HW + p], pv = p3[ch * HW + p];
+      const float d = tv - pv;
+      if (rob) s_rob2 += d * d; else s_world2 += d * d;
+      const float dm = (weighted && rob) ? d * rw : d;
+      s_main += l1 ? fabsf(dm) : dm * dm;
+      if (rob) {
+        tv *= 0.f;
+        pv *= 0.f;
+      }
+      const float ca = fminf(fmaxf(tv, 0.f), 1.f), cb = fminf(fmaxf(pv, 0.f), 1.f);
+      const float e = (ca + 1.f) * 0.5f - (cb + 1.f) * 0.5f;
+      s_se += e * e;
+    }
+  }
+  const float t0 = eval_block_sum(s_main, red), t1 = eval_block_sum(s_rob2, red), t2 = eval_block_sum(s_world2, red),
+              t3n = eval_block_sum(s_rob_n, red), t4 = eval_block_sum(s_se, red);
+  if (threadIdx.x == 0) {
+    o[0] = t0, o[1] = t1, o[2] = t2, o[3] = t3n, o[4] = t4, o[5] = ssim;
+  }
+}
+
+}  // namespace rac
+
+extern "C" int rac_eval_frames(int32_t kind, const float* pred, const float* target, const float* mask,
+                               float robot_weight, float* rows, int32_t S, int32_t B, int32_t H, int32_t W,
+                               void* stream) {
+  using namespace rac;
+  RAC_REQUIRE(kind >= 0 && kind <= 3 && pred && target && rows && S > 0 && B > 0 && H > 0 && W > 0,
+              "rac_eval_frames: bad args");
+  RAC_REQUIRE((long)S * B <= (1L << 28) && (long)H * W < (1L << 29), "rac_eval_frames: too many videos or pixels");
+  SsimWin win;
+  float gf[11];  // the window of rac_psnr_ssim: fp32 gaussian(11, 1.5) over its correctly rounded sum
+  double tot = 0.0;
+  for (int i = 0; i < 11; ++i) {
+    gf[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
+    tot += (double)gf[i];
+  }
+  const float sum = (float)tot;
+  for (int i = 0; i < 11; ++i) win.g[i] = gf[i] / sum;
+  hipLaunchKernelGGL(eval_frames_kernel, dim3(3 * S * B), dim3(EV_THREADS), 0, reinterpret_cast<hipStream_t>(stream), kind,
+                     pred, target, mask, robot_weight, rows, B, H, W, win);
+  return check_launch("rac_eval_frames");
+}
+
 RAC_DEVICE_CODE_END

@@ -3152,6 +3152,30 @@ def predict_frames(x4, prev, target, true_mask, gen_u8, true_u8, step: int, pred
     return pred
 
 
+def eval_frames(pred, target, mask, kind: int, robot_weight: float, S: int = 1, out=None) -> torch.Tensor:
+    """Everything `_eval_step` scores on one predicted frame, for S prior samples of B videos, in one launch and without
+    a host sync (`rac_eval_frames`): `pred` (S B, 3, H, W) with sample group s in rows [s B, (s+1) B), `target`
+    (B, 3, H, W) and `mask` (B, 1, H, W) or None shared by the groups.  Returns the (S B, 8) fp32 table of per-video
+    sums (`metrics.table_scalars` turns it into the logged scalars); `out`: a contiguous (S B, 8) fp32 view to fill."""
+    _require_cuda(pred)
+    f32 = torch.float32
+    n, _, H, W = pred.shape
+    B = target.shape[0]
+    ok = (S >= 1 and n == S * B and tuple(pred.shape) == (n, 3, H, W) and tuple(target.shape) == (B, 3, H, W)
+          and (mask is None or tuple(mask.shape) == (B, 1, H, W))
+          and (out is None or (tuple(out.shape) == (n, 8) and out.dtype == f32 and out.is_contiguous())))
+    if not ok:
+        raise _lib.RacError(f"eval_frames: shapes do not fit (pred {tuple(pred.shape)}, target {tuple(target.shape)}, "
+                            f"mask {None if mask is None else tuple(mask.shape)}, S {S})")
+    pred = pred.detach().to(f32).contiguous()
+    target = target.detach().to(f32).contiguous()
+    mask = None if mask is None else mask.detach().to(f32).contiguous()
+    rows = torch.empty((n, 8), device=pred.device, dtype=f32) if out is None else out
+    call("rac_eval_frames", int(kind), ptr(pred), ptr(target), ptr(mask), float(robot_weight), ptr(rows), S, B, H, W,
+         stream_ptr())
+    return rows
+
+
 class ZeroRegion(torch.autograd.Function):
     """zero_robot_region (src/utils/image.py:5-19), out of place."""
 

@@ -459,8 +459,20 @@ class PredictionTrainer(object):
         return {f"{name}/{k}": float(np.mean(v)) for k, v in losses.items()}
 
     def _eval_video(self, data, autoregressive=False):
-        """Evaluate a whole video in n_eval windows (trainer.py:490-564); ground-truth masks drive the rollout."""
+        """Evaluate a whole video in n_eval windows (trainer.py:490-564); ground-truth masks drive the rollout.
+
+        `--eval_best_of_three True` (this repository's flag, default off): an autoregressive evaluation of `--model svg`
+        under a `finetune*` experiment draws three prior samples per window, as the reference always does
+        (trainer.py:497-499), and returns the sample whose summed `autoreg_psnr` is largest (trainer.py:558-559; a
+        stable sort: ties keep the earlier sample); its index is left in `self.last_best_eval_sample`.  The robot model
+        is asked once per window.  The three samples of a window run as one batch of 3 B videos
+        (`RAC_PREDICT_BATCH_SAMPLES=0`: one after the other through the same scoring code), see `_eval_step`."""
         cf = self._config
+        num_samples = 3 if (getattr(cf, "eval_best_of_three", False) and autoregressive and cf.model == "svg"
+                            and "finetune" in cf.experiment) else 1
+        self.last_best_eval_sample = 0
+        batched = os.environ.get("RAC_PREDICT_BATCH_SAMPLES", "1") == "1"
+        sampled = [defaultdict(float) for _ in range(num_samples)]
         finetune = "finetune" in cf.experiment and (cf.model_use_mask or cf.model_use_robot_state)
         if finetune and getattr(self, "robot_model", None) is None:
             raise NotImplementedError(
@@ -492,16 +504,46 @@ class PredictionTrainer(object):
                     batch["states"], batch["pred_masks"], batch["heatmaps"] = out
                 else:
                     batch["states"], batch["pred_masks"] = out
-            for k, v in self._eval_step(batch, autoregressive).items():
-                total[k] += v
+            if num_samples == 1:
+                for k, v in self._eval_step(batch, autoregressive).items():
+                    total[k] += v
+                continue
+            if batched:
+                outs = self._eval_step(batch, autoregressive, num_samples=num_samples)
+            else:
+                outs = [self._eval_step(batch, autoregressive, num_samples=1)[0] for _ in range(num_samples)]
+            for sample, losses in zip(sampled, outs):
+                for k, v in losses.items():
+                    sample[k] += v
+        if num_samples > 1:
+            self.last_best_eval_sample = self._best_eval_sample(sampled, autoregressive and cf.model == "svg")
+            total = sampled[self.last_best_eval_sample]
         for k in total:
             total[k] /= floor(T / window)
         return total
 
+    @staticmethod
+    def _best_eval_sample(sampled, by_psnr=True):
+        """Index of the sample `_eval_video` reports (trainer.py:558-560): the largest summed `autoreg_psnr`, ties to the
+        earlier sample (`list.sort(reverse=True)` is stable); the first sample where nothing is sorted."""
+        order = list(range(len(sampled)))
+        if by_psnr:
+            order.sort(key=lambda n: sampled[n]["autoreg_psnr"], reverse=True)
+        return order[0]
+
     @torch.no_grad()
-    def _eval_step(self, data, autoregressive=False):
+    def _eval_step(self, data, autoregressive=False, num_samples=None):
         """Evaluate one n_eval snippet (trainer.py:566-734): prior-driven prediction (`force_use_prior`), optional
-        autoregressive feeding, recon / robot / world losses, PSNR, SSIM, KL.  One host sync at the end."""
+        autoregressive feeding, recon / robot / world losses, PSNR, SSIM, KL.  One host sync at the end.
+
+        `num_samples` = S (the sampled evaluation of `_eval_video`; None: the path above, untouched) rolls S prior
+        samples of the snippet as ONE batch of S B videos, as `_predict_video` does (inputs repeated per sample group,
+        `model.eps_source` asked for (S B, z, h, w) per draw, sample s in rows [s B, (s+1) B)), scores each predicted
+        frame with ONE `ops.eval_frames` launch into a (n_eval - 1, S B, 8) table, takes the KL per group on slices,
+        and returns a list of S loss dicts with this method's keys.  Every scalar is an elementwise function of a
+        video's table rows followed by sums in a fixed order, so a sample's numbers do not depend on S."""
+        if num_samples is not None:
+            return self._eval_step_sampled(data, autoregressive, int(num_samples))
         from .metrics import masked_psnr_ssim
         cf = self._config
         dev, f32 = self._device, torch.float32
@@ -569,6 +611,85 @@ class PredictionTrainer(object):
         for (name, _), v in zip(klog, vals[len(log):]):
             losses[name] = v
         return losses
+
+    @torch.no_grad()
+    def _eval_step_sampled(self, data, autoregressive, S):
+        """`_eval_step(num_samples=S)`: the rollout of `_eval_step` on S B videos, one `ops.eval_frames` launch per frame."""
+        from .metrics import table_scalars
+        cf = self._config
+        dev, f32 = self._device, torch.float32
+        if cf.model != "svg":
+            raise ValueError("only --model svg draws samples")
+        x = data["images"].to(dev, f32)
+        states = data["states"].to(dev, f32)
+        ac = data["actions"].to(dev, f32)
+        true_masks = data["masks"].to(dev, f32)
+        masks = data["pred_masks"].to(dev, f32)
+        heatmaps = data["heatmaps"].to(dev, f32) if getattr(cf, "model_use_heatmap", False) else None
+        robot_name = np.array(data["robot"])
+        all_robots = sorted(set(robot_name))
+        bs = min(cf.test_batch_size, x.shape[1])
+        self.model.init_hidden(S * bs)
+        if S > 1:  # sample group s = rows [s bs, (s+1) bs)
+            rep = lambda t: t.repeat((1, S) + (1,) * (t.dim() - 2))
+            states, ac, masks = rep(states), rep(ac), rep(masks)
+            heatmaps = rep(heatmaps) if heatmaps is not None else None
+        frame_in = lambda i: x[i] if S == 1 else x[i].repeat(S, 1, 1, 1)
+        n_steps = cf.n_eval - 1
+        H, W = x.shape[-2], x.shape[-1]
+        prefix = "autoreg" if autoregressive else "1step"
+        dontcare = "dontcare" in cf.reconstruction_loss or cf.black_robot_input
+        kind = self._loss_kind()
+        rw = cf.robot_pixel_weight if "dontcare" in cf.reconstruction_loss else 0.0
+        table = torch.empty((n_steps, S * bs, 8), device=dev, dtype=f32)
+        kls = []
+        x_pred = skip = None
+        for i in range(1, cf.n_eval):
+            x_j = x_pred if (autoregressive and i > 1) else frame_in(i - 1)
+            m_j, r_j, a_j = masks[i - 1], states[i - 1], ac[i - 1]
+            m_i, r_i = masks[i], states[i]
+            if cf.last_frame_skip:
+                skip = None
+            m_in = torch.cat([m_j, m_i], 1) if cf.model_use_future_mask else m_j
+            r_in = (r_j, r_i) if cf.model_use_future_robot_state else r_j
+            hm_in = None
+            if heatmaps is not None:
+                hm_in = torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap else heatmaps[i - 1]
+            x4, curr_skip, mu, logvar, mu_p, logvar_p = self.model.forward_maps(
+                x_j, m_in, r_in, hm_in, a_j, True, r_i, skip, force_use_prior=True, zero_mask=m_j if dontcare else None)
+            x_pred = ops.Composite.apply(x4, x_j.contiguous())
+            if i <= cf.n_past:
+                skip = curr_skip
+            # robot region blacked with, and the errors split by, the true mask
+            ops.eval_frames(x_pred, x[i], true_masks[i], kind, rw, S, out=table[i - 1])
+            for n in range(S):
+                sl = slice(n * bs, (n + 1) * bs)
+                kls.append(ops.KLLoss.apply(mu[sl], logvar[sl], mu_p[sl], logvar_p[sl], bs)[0])
+        groups = table.view(n_steps, S, bs, 8)
+        scal = table_scalars(groups, kind, 3 * H * W)
+        names = [f"{prefix}_{k}" for k in ("recon_loss", "robot_loss", "world_loss", "psnr", "ssim")]
+        cols = [scal[k] for k in ("recon_loss", "robot_loss", "world_loss", "psnr", "ssim")]
+        if len(all_robots) > 1:
+            for r in all_robots:
+                sub = table_scalars(groups, kind, 3 * H * W, index=np.nonzero(robot_name == r)[0])
+                names += [f"{prefix}_{r}_robot_loss", f"{prefix}_{r}_world_loss"]
+                cols += [sub["robot_loss"], sub["world_loss"]]
+        names.append(f"{prefix}_kld")
+        cols.append(torch.stack(kls).view(n_steps, S))
+        vals = torch.stack(cols).cpu().tolist()  # [key][step][sample]: the one host sync
+        outs = []
+        for n in range(S):
+            losses = defaultdict(float)
+            for name, per_step in zip(names, vals):
+                for step in per_step:
+                    losses[name] += step[n]
+                losses[name] = losses[name] / n_steps
+            if autoregressive:
+                for i in range(1, cf.n_eval):
+                    for key, col in (("psnr", 3), ("ssim", 4), ("world_loss", 2)):
+                        losses[f"{i}_step_{key}"] = vals[col][i - 1][n]
+            outs.append(losses)
+        return outs
 
     # ------------------------------------------------------------ video export
     def predict_video(self, data):
