@@ -158,7 +158,8 @@ int rac_conv2d_fwd_split(const rac_conv_args* a, const uint32_t* a_amax0, const 
  * (ConvEncoder's `mp` behind the last vgg_layer of c1 / c2 / c3, vgg_64.py:104-129, frozen model): the unrolled 3x3 kernels
  * on maps larger than a tile, full 128-pixel tiles and column blocks, split_k 1, no statistics, an output below 4 GiB, a
  * 16-row block and the block under it held by one wave (W = 16, 32, or 2-D tiles).  0 otherwise: call rac_maxpool2_fwd.
- * Nothing is launched.  The pooled tensor's maximum is bounded by the output's (out_amax): no separate slot. */
+ * A pure host query: the arguments are checked, nothing behind a pointer is read, no device is touched and nothing is
+ * launched (it answers on a machine without a GPU).  The pooled tensor's maximum is bounded by the output's (out_amax): no separate slot. */
 int rac_conv2d_fwd_split_pool_ok(const rac_conv_args* a, int32_t w_cin);
 /* The FROZEN model's ConvLSTM cell in one launch (lstm.py:129-149 without a tape): the gate conv of
  * rac_conv2d_fwd_split with the cell arithmetic in its epilogue,

@@ -61,16 +61,6 @@ __host__ __device__ __forceinline__ int scale_exp(unsigned amax_bits) {
 }
 __device__ __forceinline__ float pow2f(int k) { return __builtin_bit_cast(float, (unsigned)(k + 127) << 23); }
 
-#ifndef RAC_EPILOGUE_FAST  // the conv kernels' predicate-free epilogue with buffer stores (0: the general path always)
-#define RAC_EPILOGUE_FAST 1
-#endif
-// timing builds of the persistent rows kernel (tools/build_variant.sh ... -DRAC_EXP_PERSIST=<bits>; results are WRONG):
-// 1 epilogue without its stores, 2 no epilogue, 4 staging with one conversion instead of the split, 8 fragment reads at tap 0
-// only, 16 no weight loads inside the loop, 32 the next tile = this tile (no per-tile index arithmetic, staging loads hit L2), 64 the arithmetic done but this tile's addresses used
-#ifndef RAC_EXP_PERSIST
-#define RAC_EXP_PERSIST 0
-#endif
-
 // eight fp32 values (two 16-byte vectors) * scale -> two fp16 parts, packed as 16-byte MFMA operand vectors
 __device__ __forceinline__ void split8h(u32x4 lo, u32x4 hi, float s, u32x4 (&q)[2]) {
   const unsigned w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
@@ -80,7 +70,7 @@ __device__ __forceinline__ void split8h(u32x4 lo, u32x4 hi, float s, u32x4 (&q)[
     const float v = __builtin_bit_cast(float, w[j]) * s;
     const _Float16 a = (_Float16)v;
     h1[j] = a;
-    h2[j] = (RAC_EXP_PERSIST & 4) ? a : (_Float16)(v - (float)a);
+    h2[j] = (_Float16)(v - (float)a);
   }
   q[0] = __builtin_bit_cast(u32x4, h1);
   q[1] = __builtin_bit_cast(u32x4, h2);
@@ -195,8 +185,7 @@ __device__ __forceinline__ void conv16_epilogue_body(const Conv16P& p, const f32
   // costs of the narrow layers' kernels add up, profiles/r04_persist_decomposition.md: this is the largest of them.)
   const int blk_last = min(mb0 + MBLK, nmb) - 1;  // the wave's last live block
   const int m_last = ym_hw ? m0 + ym_hw + blk_last * 8 + 7 : seg_row_pixel(p, m0, blk_last * 16) + 15;
-  if (RAC_EPILOGUE_FAST && !p.stats && blk_last >= mb0 && m_last < p.M && ncol0 + NBLK * 16 <= NS &&
-      (long)p.M * NS * 4 < (1l << 32)) {
+  if (!p.stats && blk_last >= mb0 && m_last < p.M && ncol0 + NBLK * 16 <= NS && (long)p.M * NS * 4 < (1l << 32)) {
     unsigned voff[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -303,7 +292,7 @@ __device__ __forceinline__ void conv16_epilogue_body(const Conv16P& p, const f32
         v = v > 0.f ? v : slope * v;
         if (SIG) v = sigmoid_acc(v);
         if (ok) {
-          if (!(RAC_EXP_PERSIST & 1)) p.out0[(long)m * NS + n] = v;
+          p.out0[(long)m * NS + n] = v;
           mxb[mb] = max(mxb[mb], absbits(v));
         }
       }
@@ -439,48 +428,6 @@ __device__ __forceinline__ void conv16_lstm_epilogue(const Conv16P& p, const f32
 // the block's fragment reads and MFMAs are skipped -- 15 % of a 5x5 conv's products on 8-row maps (image rows 0, 1, 6, 7
 // lose 2, 1, 1, 2 of their 5 kernel rows), 8 % of a 3x3 conv's -- instead of multiplying zero rows.  A tap's shift
 // stays one wave-uniform offset (16 rows per image row); the epilogue maps rows back to the tensor's (image, y, x) order.
-#ifndef RAC_TILE_READ_ALL
-#define RAC_TILE_READ_ALL 0
-#endif
-#ifndef RAC_EXP_ROWS_NOZERO
-#define RAC_EXP_ROWS_NOZERO 0
-#endif
-#ifndef RAC_WGRAD_ROLL  // weight-gradient kernel: input fragments rolled through the taps in halves (0: read per tap, then wait)
-#define RAC_WGRAD_ROLL 1
-#endif
-#ifndef RAC_WGRAD_LATE_BLOCKS  // 5x5 128-co weight gradient on operand parts: MFMA blocks in front of the last one that take store pieces
-#define RAC_WGRAD_LATE_BLOCKS 2
-#endif
-#ifndef RAC_EXP_WGRAD  // timing builds of the weight-gradient kernel (wrong results): 1 = no barrier inside the loop, 2 = no global loads inside the loop, 4 = no LDS stores inside the loop
-#define RAC_EXP_WGRAD 0
-#endif
-#ifndef RAC_EXP_TILE  // timing builds of the tile kernel (wrong results): 1 = activations requested for the first chunk only, 2 = every chunk requests the FIRST chunk's addresses (L2 hits)
-#define RAC_EXP_TILE 0
-#endif
-#ifndef RAC_EXP_ROWS_NOSTORE
-#define RAC_EXP_ROWS_NOSTORE 0
-#endif
-#ifndef RAC_EXP_ROWS_NOB
-#define RAC_EXP_ROWS_NOB 0
-#endif
-#ifndef RAC_TILE_A_BEHIND  // tile kernel's unrolled instances: activations requested behind a chunk's first weight request
-#define RAC_TILE_A_BEHIND 1
-#endif
-#ifndef RAC_A_REQUEST_TAP  // the tap of a chunk behind whose weight request the next chunk's activations are requested
-#define RAC_A_REQUEST_TAP 0
-#endif
-#ifndef RAC_ROWS_GENERIC_SEG
-#define RAC_ROWS_GENERIC_SEG 1
-#endif
-#ifndef RAC_ROWS_REFILL  // the rows kernel's weight sets refilled in place, quarter by quarter (0: one set kept free for the requests)
-#define RAC_ROWS_REFILL 1
-#endif
-#ifndef RAC_ROWS_REFILL_PIN  // scheduling barriers around a quarter's refill request: 1 = before, 2 = behind
-#define RAC_ROWS_REFILL_PIN 3
-#endif
-#ifndef RAC_ROWS_RING3  // three weight register sets in the 128-column rows kernel too (needs its registers freed elsewhere)
-#define RAC_ROWS_RING3 0
-#endif
 // KU = 3: the 9 taps of a 3x3 conv's chunk unrolled (K ranges are whole chunks): tap constants, and every wait exact.
 template <int WM, bool FULL, bool YM = false, int KU = 0>
 __global__ __launch_bounds__(256, 2) void conv16_tile_kernel(Conv16P p) {
@@ -678,9 +625,13 @@ __global__ __launch_bounds__(256, 2) void conv16_tile_kernel(Conv16P p) {
     // follow the request directly, `vmcnt(3)` ... `(0)`, and since loads return in order that also drained the 16 weight loads
     // in flight for the next two steps -- an exposed L2 round trip per chunk (9 steps of a 3x3 conv, 25 of a 5x5).
     auto request_a = [&](int c) {
-      if (!(RAC_EXP_TILE & 1) && c * p.taps < kc_end) issue_a((RAC_EXP_TILE & 2) ? kc_begin / p.taps : c);
+      if (c * p.taps < kc_end) issue_a(c);
+      // (names kc_begin so that the closure still captures it, as it did while a removed timing variant read it here: no
+      // instruction comes of it, but without the capture the compiler allocates the registers of the <2, false, true, 5>
+      // instance differently, and this text is held to the device code that was measured)
+      (void)kc_begin;
     };
-    if (!(KU != 0 && RAC_TILE_A_BEHIND)) request_a(cc + 1);
+    if (KU == 0) request_a(cc + 1);
     // (unrolled instances: the request sits behind the weight request of a chunk's FIRST step instead -- loads return in order,
     // and the first weight set that has to wait for the activations is then the one read three steps from the request, not two)
 
@@ -709,12 +660,11 @@ __global__ __launch_bounds__(256, 2) void conv16_tile_kernel(Conv16P p) {
         for (int t = 0; t < 4; ++t) {
           const int mb = 4 * h + t;
           if (!FULL && (mb >= RBL || mbw + mb >= nmb)) continue;  // wave-uniform
-#if !RAC_TILE_READ_ALL  // (reading dead blocks too -- straight-line LDS traffic, exact waits -- measured +0 % on 5x5, +1 % on 3x3)
-          // the tap leaves the image: no work.  (Dropping the test for the taps of the kernel's centre row, which never leave
+          // the tap leaves the image: no work.  (Reading dead blocks too -- straight-line LDS traffic, exact waits -- measured
+          // +0 % on 5x5, +1 % on 3x3.  Dropping the test for the taps of the kernel's centre row, which never leave
           // -- a compile-time fact in the unrolled instances -- merges such a step's four row blocks into one basic block of 48
           // MFMAs, and the compiler's schedule of that block is SLOWER: 12.55 -> 13.2 ms on the 5x5 gate GEMM at M = 64 000.)
           if (YM && (unsigned)(mbw + mb + ky - p.pad) >= (unsigned)p.H) continue;
-#endif
           const int ao = YM ? shift + mb * (16 * T16Y_PITCH) : ((amask[mb] & bit) ? shift + mb * 256 : zr);
 #pragma unroll
           for (int part = 0; part < 2; ++part)
@@ -738,7 +688,7 @@ __global__ __launch_bounds__(256, 2) void conv16_tile_kernel(Conv16P p) {
 #pragma unroll
         for (int t9 = 0; t9 < 9; ++t9) {
           if (t9 == 0) load_b(b2, cc * 9 + 2);
-          if (RAC_TILE_A_BEHIND && t9 == 0 && more) request_a(cc + 1);
+          if (t9 == 0 && more) request_a(cc + 1);
           if (t9 % 3 == 1) load_b(b0, cc * 9 + t9 + 2);
           if (t9 % 3 == 2) load_b(b1, cc * 9 + t9 + 2);
           if (t9 % 3 == 0 && t9) load_b(b2, cc * 9 + t9 + 2);
@@ -748,7 +698,6 @@ __global__ __launch_bounds__(256, 2) void conv16_tile_kernel(Conv16P p) {
           store_a(cur ^ 1);
           __syncthreads();
           cur ^= 1;
-          if (!RAC_TILE_A_BEHIND) request_a(cc + 2);
         }
       }
     } else if constexpr (KU == 5) {
@@ -771,7 +720,7 @@ __global__ __launch_bounds__(256, 2) void conv16_tile_kernel(Conv16P p) {
         };
         for (int g8 = 0; g8 < 8; ++g8) {
           load_b(s2, kc0 + t + 2);
-          if (RAC_TILE_A_BEHIND && g8 == 0 && more) request_a(c + 1);
+          if (g8 == 0 && more) request_a(c + 1);
           stepk(s0, t, y, x);
           adv();
           load_b(s0, kc0 + t + 2);
@@ -787,7 +736,6 @@ __global__ __launch_bounds__(256, 2) void conv16_tile_kernel(Conv16P p) {
           store_a(cur ^ 1);
           __syncthreads();
           cur ^= 1;
-          if (!RAC_TILE_A_BEHIND) request_a(c + 2);
         }
       };
       while (cc < c_end) {
@@ -1144,9 +1092,6 @@ __global__ __launch_bounds__(256, 2) void first16_kernel(const float* __restrict
 // HBM round trip alone is 4-6 us of a 22 us tile) and issues 3.4 other VALU instructions per MFMA (staging with its
 // 2x halo, tap addressing, the epilogue), which share the SIMD's issue port with the MFMAs.  Dropping the fragment
 // reads, the weight loads or the MFMAs themselves from the loop changes the kernel time by 5-10 % each.
-#ifndef RAC_ROWS_PIN
-#define RAC_ROWS_PIN 1
-#endif
 // KSF: kernel size of the FAST form (3, or 5: the 5x5 ConvLSTM gate convs on the 16x16 latents of a 128x128 model --
 // round 5; whole-row tiles only, 128-column workgroups only).
 template <int NV, int WM, int NT, int D, bool FAST = false, int KSF = 3>
@@ -1228,9 +1173,7 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_kernel(Conv16P p) {
   const int pplane = 4 * cplane;
   const int abuf = 2 * pplane;           // one buffer
   if constexpr (FAST) {
-#if !RAC_EXP_ROWS_NOZERO  // (timing / counter builds: which LDS stream of this kernel conflicts?  tools/build_variant.sh)
     for (int o = tid * 16; o < 2 * abuf; o += 4096) *reinterpret_cast<u32x4*>(lds_raw + o) = u32x4{0u, 0u, 0u, 0u};
-#endif
     __syncthreads();  // (the staging below writes some of the same rows from other threads)
   } else {  // zero rows of both buffers: 2 buffers x 2 parts x 4 groups x 16 rows = 256 vectors
     const int pl = tid >> 4, r = tid & 15;
@@ -1323,13 +1266,9 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_kernel(Conv16P p) {
       if (s_off[i] < 0) continue;
       u32x4 q[2];
       split8h(ra[2 * i], ra[2 * i + 1], sa, q);
-#if !RAC_EXP_ROWS_NOSTORE
 #pragma unroll
       for (int part = 0; part < 2; ++part)
         *reinterpret_cast<u32x4*>(lds_raw + buf * abuf + part * pplane + s_off[i]) = q[part];
-#else
-      if (q[0].x == 0x12345678u && q[1].y == 0x9abcdef0u) *reinterpret_cast<u32x4*>(lds_raw) = q[0];
-#endif
     }
   };
 
@@ -1425,14 +1364,15 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_kernel(Conv16P p) {
       // MFMAs that read it: each tap then waited out an L2 round trip (seen in the ISA: s_waitcnt vmcnt(7) straight after
       // eight loads).  Nine taps are odd, so with two sets the set of a tap alternates between chunks: the chunk body exists
       // for both parities.  The narrower forms keep three sets, two taps ahead.
-      // RAC_ROWS_REFILL: no set is kept free for the requests -- all R sets are in flight, and a set is refilled IN PLACE, one
-      // 16-column quarter (two 16-byte loads) at a time, as soon as the MFMAs that read that quarter have been issued
-      // (the MFMAs of a tap run column-block-major for this): the quarter for tap t + R is requested 1/4 .. 4/4 of the way
-      // through tap t and first read the same way through tap t + R -- R - 1/4 taps of cover for every quarter instead
-      // of R - 1, from the same registers.  +2-3 % on the 16x16 256-channel layers, ~1 % on the 32x32 ones; a SIX-set ring on
-      // the 64-column form (16 VGPRs per set) measured exactly the three-set time: L2 latency is covered, what the weight
-      // stream costs these kernels (a timing build without it: +12 % here, +33 % before the refill) is not waiting time.
-      constexpr int R = (NT == 2 && !RAC_ROWS_RING3) ? 2 : 3, AHEAD = RAC_ROWS_REFILL ? R : R - 1;
+      // No set is kept free for the requests (the form before this one kept one): all R sets are in flight, and a set is
+      // refilled IN PLACE, one 16-column quarter (two 16-byte loads) at a time, as soon as the MFMAs that read that quarter
+      // have been issued (the MFMAs of a tap run column-block-major for this): the quarter for tap t + R is requested 1/4 ..
+      // 4/4 of the way through tap t and first read the same way through tap t + R -- R - 1/4 taps of cover for every quarter
+      // instead of R - 1, from the same registers.  +2-3 % on the 16x16 256-channel layers, ~1 % on the 32x32 ones; a SIX-set
+      // ring on the 64-column form (16 VGPRs per set) measured exactly the three-set time: L2 latency is covered, what the
+      // weight stream costs these kernels (a timing build without it measured +12 % here, +33 % before the refill) is not
+      // waiting time.
+      constexpr int R = NT == 2 ? 2 : 3, AHEAD = R;
       u32x4 bs[R][4 * NT];
       issue_a(c_begin);
 #pragma unroll
@@ -1456,15 +1396,10 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_kernel(Conv16P p) {
 #pragma unroll
         for (int tap = 0; tap < TAPSF; ++tap) {
           const int ky = tap / KSF, kx = tap % KSF;
-#if !(RAC_EXP_ROWS_NOB) && !RAC_ROWS_REFILL  // (timing build: the weight fragments loaded once per workgroup)
-          load_b(bs[(tap + AHEAD + P) % R], min(kc0 + tap + AHEAD, kc_end - 1));
-#endif
-#if RAC_ROWS_PIN
           // pin the requests here: in this one large basic block the scheduler otherwise moves them towards their use.
           // (Also pinning a tap's fragment reads before its MFMAs, or rotating them through the tap in halves as
           // conv16_rows_persist_kernel does: +4 % on the 64-column form, nothing on the 128-column one -- not done.)
           __builtin_amdgcn_sched_barrier(0);
-#endif
           const int shift = ((ky - PF) * WP + (kx - PF)) * 16 + bufo;  // wave-uniform: the tap in the padded rows
           f16x8 fb[NB][2];
 #pragma unroll
@@ -1482,27 +1417,14 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_kernel(Conv16P p) {
             for (int part = 0; part < 2; ++part)
               fa[t][part] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(lds_raw + ao + part * pplane));
           }
-#if RAC_ROWS_REFILL
 #pragma unroll
           for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
             for (int t = 0; t < MB; ++t) acc[t][nb] = mma3(fa[t], fb[nb], acc[t][nb]);
-#if RAC_ROWS_REFILL_PIN & 1
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-#if !(RAC_EXP_ROWS_NOB)
+            __builtin_amdgcn_sched_barrier(0);  // (the quarter's refill request pinned on both sides)
             load_b_quarter(bs[(tap + P) % R], nb, min(kc0 + tap + R, kc_end - 1));
-#endif
-#if RAC_ROWS_REFILL_PIN & 2
             __builtin_amdgcn_sched_barrier(0);
-#endif
           }
-#else
-#pragma unroll
-          for (int t = 0; t < MB; ++t)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[t][nb] = mma3(fa[t], fb[nb], acc[t][nb]);
-#endif
         }
         if (more) {
           store_a(cur ^ 1);
@@ -1572,9 +1494,7 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_kernel(Conv16P p) {
             if (wm * MB + HB * h + t >= nmb) continue;
             acc[HB * h + t][nb] = mma3(fa[t], fb[nb], acc[HB * h + t][nb]);
           }
-#if RAC_ROWS_GENERIC_SEG
           __builtin_amdgcn_sched_barrier(0);  // one row block's MFMAs at a time (see the tile kernel's note on block branches)
-#endif
         }
       }
       if (last_tap && more) {
@@ -1764,7 +1684,6 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_persist_kernel(Conv16P p) 
   issue_a(0, cur_t);
   load_b(bs[0], kc_begin);
   load_b(bs[1], min(kc_begin + 1, kc_end - 1));
-  if (RAC_EXP_PERSIST & 16) load_b(bs[2], min(kc_begin + 2, kc_end - 1));
   int cur = 0;
   // A fragments rotate through the tap in halves: the second half's reads are issued before the first half's MFMAs, the NEXT
   // tap's first half before the second half's MFMAs, pinned with scheduling barriers.  (Left alone, the scheduler issued
@@ -1786,17 +1705,7 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_persist_kernel(Conv16P p) 
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < HB; ++t) read_frag(t, 0, cur * abuf);
-    if (has_next) {
-      if (RAC_EXP_PERSIST & 32)
-        nxt_t = cur_t;
-      else
-        setup(next_bx, nxt_t);
-      if (RAC_EXP_PERSIST & 64) {  // the arithmetic is done, the addresses are this tile's again (loads hit L2)
-        const int keep = nxt_t.m0 ^ nxt_t.pix[0];
-        nxt_t = cur_t;
-        if (keep == 0x7fffffff) nxt_t.ka += 1;  // (keeps setup() alive)
-      }
-    }
+    if (has_next) setup(next_bx, nxt_t);
     f32x4 acc[MB][NB];
 #pragma unroll
     for (int i = 0; i < MB; ++i)
@@ -1810,8 +1719,8 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_persist_kernel(Conv16P p) 
         // the ring wraps to taps 0 and 1 of chunk 0 behind the last chunk: the next tile multiplies the same weights
         int knext = kc0 + tap + 2;
         knext = knext >= kc_end ? knext - kc_end : knext;
-        if (!(RAC_EXP_PERSIST & 16)) load_b(bs[(tap + 2) % 3], knext);
-        if (tap == RAC_A_REQUEST_TAP) {
+        load_b(bs[(tap + 2) % 3], knext);
+        if (tap == 0) {
           // the next chunk's activations are requested BEHIND this tap's weight request: loads return in order, so the first
           // weight set that has to wait for them is the one requested at the next tap and read three taps from here (requested
           // in front of this tap's, it was the one read two taps from here)
@@ -1829,10 +1738,8 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_persist_kernel(Conv16P p) 
 #pragma unroll
             for (int part = 0; part < 2; ++part)
               fb[j2 * 2 + nb][part] = __builtin_bit_cast(f16x8, bs[tap % 3][(j2 * 2 + part) * 2 + nb]);
-        if (!(RAC_EXP_PERSIST & 8) || tap == 0) {
 #pragma unroll
-          for (int t = HB; t < MB; ++t) read_frag(t, tap, cur * abuf);
-        }
+        for (int t = HB; t < MB; ++t) read_frag(t, tap, cur * abuf);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < HB; ++t)
@@ -1844,7 +1751,7 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_persist_kernel(Conv16P p) 
           __syncthreads();
           cur ^= 1;
         }
-        if ((tap < 8 || more) && (!(RAC_EXP_PERSIST & 8) || tap == 8)) {
+        if (tap < 8 || more) {
 #pragma unroll
           for (int t = 0; t < HB; ++t) read_frag(t, (tap + 1) % 9, cur * abuf);
         }
@@ -1856,19 +1763,8 @@ __global__ __launch_bounds__(256, 2) void conv16_rows_persist_kernel(Conv16P p) 
       }
     }
     const int img = p.per_image ? cur_t.m0 / p.HW : 0;
-    if (RAC_EXP_PERSIST & 2) {
-      unsigned mx = 0;
-#pragma unroll
-      for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) mx = max(mx, absbits(acc[i][j][r]));
-      if (p.out_amax) amax_commit(mx, p.out_amax + img);
-    } else {
-      conv16_epilogue(p, acc, cur_t.m0, wm * MB, nmb, n0 + wn * NT * 32, 0, pow2f(-cur_t.ka), pow2f(-kw), pre, nullptr,
-                      p.out_amax ? p.out_amax + img : nullptr);
-    }
+    conv16_epilogue(p, acc, cur_t.m0, wm * MB, nmb, n0 + wn * NT * 32, 0, pow2f(-cur_t.ka), pow2f(-kw), pre, nullptr,
+                    p.out_amax ? p.out_amax + img : nullptr);
     if (!has_next) break;
     // the next tile's first chunk goes to the buffer nobody reads any more (the last chunk sits in `cur`)
     cur ^= 1;
@@ -2390,23 +2286,21 @@ __global__ __launch_bounds__(256, 2) void wgrad16_kernel(Wgrad16P p) {
       // (the allocator spills ACCUMULATORS to scratch if pieces sit between its blocks): its pieces follow the last
       // blocks, where the fragment registers are dead
       // (fp32 operands add the conversion's temporaries: all pieces behind the last block there)
-      constexpr int LATE = PRE ? RAC_WGRAD_LATE_BLOCKS : 0;
+      // LATE: on operand parts, the MFMA blocks in front of the last one that take store pieces
+      constexpr int LATE = PRE ? 2 : 0;
       constexpr int FIRST = AHEAD == 2 ? 0 : NB - 1 - LATE;
       constexpr int NSLOT = AHEAD == 2 ? NB - 1 : LATE + 1;
       const bool st_dy = s + 1 < S, st_x = s + PAD + 1 < S;
-      if (!(RAC_EXP_WGRAD & 2)) {
-        if (s + AHEAD < S) issue_dy(rdS[LSET]);
-        if (s + PAD + AHEAD < S) issue_x(rxS[LSET]);
-      }
+      if (s + AHEAD < S) issue_dy(rdS[LSET]);
+      if (s + PAD + AHEAD < S) issue_x(rxS[LSET]);
       auto pieces_behind = [&](int blk) {  // (blk is a compile-time constant at every call site)
-        if (RAC_EXP_WGRAD & 4) return;
 #pragma unroll
         for (int j = 0; j < 6; ++j)
           if (FIRST + (j * NSLOT) / 6 == blk)
             stage_piece(j, rdS[SSET], rxS[SSET], (PH + 1) & 1, (PH + PAD + 1) % NR, st_dy, st_x);
       };
       f16x8 fa[4][2];
-      if constexpr (NU == 2 && RAC_WGRAD_ROLL) {
+      if constexpr (NU == 2) {
         // The input fragments roll through the taps in halves: the 16-ci block u of tap k + 1 is read into the registers of
         // block u of tap k as soon as that block's 12 MFMAs are issued, under the 12 MFMAs of the other block -- every tap's
         // fragments are in flight for half a tap before their first use instead of being waited for in front of it.  Reads
@@ -2465,7 +2359,7 @@ __global__ __launch_bounds__(256, 2) void wgrad16_kernel(Wgrad16P p) {
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      if (!(RAC_EXP_WGRAD & 1)) __syncthreads();
+      __syncthreads();
       c = (c + 1 == p.W) ? 0 : c + 1;
       ++s;
     };
@@ -2896,21 +2790,46 @@ static int rows_tile_m(int H, int W) {
   return 0;
 }
 
+// a whole-row tile with its halo fits the LDS image's 1024 / 4 staged rows
+static bool rows_fit(int H, int W, int ksize) {
+  const int tm = W <= 128 ? rows_tile_m(H, W) : 0;
+  return tm && (tm + 2 * (ksize / 2) * W) * 4 <= 1024;
+}
+
+// the rows kernels' dynamic LDS ceiling: 2 buffers x 2 parts x 4 channel groups x (256 staged + 16 zero rows) x 16 B
+static constexpr int ROWS_LDS_MAX = 2 * 2 * 4 * (256 + 16) * 16;
+
+// raises a kernel's dynamic LDS limit (the callers do it once per kernel, behind a static flag)
+template <typename F>
+static int raise_lds_limit(F* fn, int bytes) {
+  const void* f = reinterpret_cast<const void*>(fn);
+  const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) return RAC_OK;
+  set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
+  return RAC_ELAUNCH;
+}
+
+// an integer environment switch (unset: dflt).  The on / off switches are its value != 0: "=0 turns it off" ones default
+// to 1.  Read once per process where the caller keeps the answer in a static, on every call where a test toggles it.
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
 extern "C" int rac_conv2d_split_supported(int32_t H, int32_t W, int32_t ksize, int32_t Cin, int32_t Cout, int32_t a_split) {
   if (H <= 0 || W <= 0 || ksize < 3 || ksize > 5 || !(ksize & 1) || Cin % 32 || Cout % 32) return 0;
   if (a_split > 0 && a_split < Cin && a_split % 32) return 0;
   const int HW = H * W;
   if (HW <= 128) return ((128 / HW) * HW) % 16 == 0;
-  const int tm = W <= 128 ? rows_tile_m(H, W) : 0;
-  if (tm && (tm + 2 * (ksize / 2) * W) * 4 <= 1024) return 1;
+  if (rows_fit(H, W, ksize)) return 1;
   return ksize == 3 && W >= 64 && W % 16 == 0 && H % 8 == 0;  // 2-D tiles of the unrolled 3x3 form
 }
 
 static int conv16_launch(const rac_conv_args* a, const uint32_t* a_amax0, const uint32_t* a_amax1, int64_t w_part_stride,
                          int32_t w_cin, const uint32_t* w_amax, uint32_t* out_amax, const float* lstm_c_prev, float* lstm_h,
                          float* lstm_c, void* stream, bool pool_query = false) {
-  // pool_query: nothing is launched; the return value says whether this conv can write its own 2 x 2 max-pooled output
-  // (1) or not (0) -- rac_conv2d_fwd_split_pool_ok
+  // pool_query: no device call is made (the return sits in front of the first one); the return value says whether this
+  // conv can write its own 2 x 2 max-pooled output (1) or not (0) -- rac_conv2d_fwd_split_pool_ok
   RAC_REQUIRE(a && a->mode == RAC_CONV_FWD, "rac_conv2d_fwd_split: forward mode only");
   RAC_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0 && a->a0 && a->w && (a->out0 || lstm_h) && a_amax0 &&
                   w_amax,
@@ -2961,23 +2880,22 @@ static int conv16_launch(const rac_conv_args* a, const uint32_t* a_amax0, const 
   p.w_nchunks = p.taps * (w_cin / SBK);
   p.cps = cdiv(p.nchunks, p.split_k);
   RAC_REQUIRE((long)(n_rows / 32) * p.w_nchunks * 2048L < 0xFFFFFF00L, "rac_conv2d_fwd_split: weight part too large");
-  static const char* xg = getenv("RAC_XCD_GROUP");
-  const bool want_xcd = xg ? atoi(xg) != 0 : true;
+  static const bool want_xcd = env_int("RAC_XCD_GROUP", 1);
   if (p.HW > 128) {
     // 2-D tiles (8 image rows x 16 pixels + a one-pixel halo: 180 staged pixels per 128) for the unrolled 3x3 form on
     // maps 64 or more pixels wide: a whole-row tile stages (rows + 2) W pixels -- 264 per 128 on a 64-wide map -- and has
     // no room at all for a 128-wide one (its halo alone is 256 pixels).  RAC_ROWS_TILE2D=0: whole-row tiles only.
-    const char* no2d = getenv("RAC_ROWS_TILE2D");
-    const bool rows_fit = a->W <= 128 && rows_tile_m(a->H, a->W) && (rows_tile_m(a->H, a->W) + 2 * p.pad * a->W) * 4 <= 1024;
-    static const int min_w2d = [] { const char* e = getenv("RAC_ROWS_TILE2D_MINW"); return e ? atoi(e) : 64; }();
-    bool tile2d = a->ksize == 3 && a->W >= min_w2d && a->W % 16 == 0 && a->H % 8 == 0 && !(no2d && atoi(no2d) == 0 && rows_fit);
+    const bool no2d = !env_int("RAC_ROWS_TILE2D", 1);  // (every call: the tests toggle it)
+    const bool fits = rows_fit(a->H, a->W, a->ksize);
+    static const int min_w2d = env_int("RAC_ROWS_TILE2D_MINW", 64);
+    bool tile2d = a->ksize == 3 && a->W >= min_w2d && a->W % 16 == 0 && a->H % 8 == 0 && !(no2d && fits);
     if (tile2d && p.cps % 9 != 0) {
-      if (rows_fit)
+      if (fits)
         tile2d = false;  // a K split that cuts a channel chunk: the generic loop on whole-row tiles
       else
         p.cps = cdiv(p.cps, 9) * 9;  // (only whole chunks per split; the last splits may be short or empty)
     }
-    RAC_REQUIRE(tile2d || rows_fit, "rac_conv2d_fwd_split: this map needs 2-D tiles (3x3, W %% 16 == 0, H %% 8 == 0)");
+    RAC_REQUIRE(tile2d || fits, "rac_conv2d_fwd_split: this map needs 2-D tiles (3x3, W %% 16 == 0, H %% 8 == 0)");
     if (tile2d) {
       p.seg_w = 16, p.seg_h = 8;
       p.seg_tx = a->W / 16, p.seg_tpi = (a->H / 8) * p.seg_tx;
@@ -3001,38 +2919,21 @@ static int conv16_launch(const rac_conv_args* a, const uint32_t* a_amax0, const 
     static const rows_fn fast5_fns[3] = {conv16_rows_kernel<2, 2, 2, 3, true, 5>, conv16_rows_kernel<3, 2, 2, 3, true, 5>,
                                          conv16_rows_kernel<4, 2, 2, 3, true, 5>};
     size_t lds_rows = (size_t)2 * 2 * 4 * (nrows + 16) * 16;
-    static bool rows_attr = false;
-    if (!rows_attr) {
-      for (int i = 0; i < 21; ++i) {
-        const rows_fn f = i < 9 ? fns[i / 3][i % 3] : (i < 18 ? fast_fns[(i - 9) / 3][i % 3] : fast5_fns[i - 18]);
-        if (!f) continue;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(f),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           2 * 2 * 4 * (256 + 16) * 16);
-        if (e != hipSuccess) {
-          set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-          return RAC_ELAUNCH;
-        }
-      }
-      rows_attr = true;
-    }
     const int width = p.N <= 32 ? 2 : (p.N <= 64 ? 1 : 0);
     dim3 grid(cdiv(p.M, p.tile_m), cdiv(p.N, width == 2 ? 32 : (width == 1 ? 64 : 128)), p.split_k);
     p.xcd_group = want_xcd && grid.x > 1 && (grid.y * grid.z) % 8 == 0;
-    static const char* nopair = getenv("RAC_ROWS_PAIR_XCD");  // (=0: hardware order for the two-column-tile layers)
-    if (want_xcd && !p.xcd_group && grid.y == 2 && grid.z == 1 && grid.x >= 64 && !(nopair && atoi(nopair) == 0)) p.xcd_group = 2;
-    static const char* nohalo1 = getenv("RAC_ROWS_HALO_XCD");  // (=0: hardware order for the one-column-tile layers)
-    if (want_xcd && !p.xcd_group && grid.y == 1 && grid.z == 1 && grid.x >= 128 && !(nohalo1 && atoi(nohalo1) == 0))
-      p.xcd_group = 6;
-    static const char* nofast = getenv("RAC_ROWS_GENERIC");  // A/B switch: always the generic loop
+    static const bool pair = env_int("RAC_ROWS_PAIR_XCD", 1);  // (=0: hardware order for the two-column-tile layers)
+    if (want_xcd && !p.xcd_group && grid.y == 2 && grid.z == 1 && grid.x >= 64 && pair) p.xcd_group = 2;
+    static const bool halo1 = env_int("RAC_ROWS_HALO_XCD", 1);  // (=0: hardware order for the one-column-tile layers)
+    if (want_xcd && !p.xcd_group && grid.y == 1 && grid.z == 1 && grid.x >= 128 && halo1) p.xcd_group = 6;
+    static const bool nofast = env_int("RAC_ROWS_GENERIC", 0);  // A/B switch: always the generic loop
     rows_fn fn = fns[width][nv - 2];
-    const bool fast = a->ksize == 3 && p.tile_m == 128 && p.cps % 9 == 0 && fast_fns[width][nv - 2] &&
-                      (tile2d || !(nofast && atoi(nofast)));
+    const bool fast = a->ksize == 3 && p.tile_m == 128 && p.cps % 9 == 0 && fast_fns[width][nv - 2] && (tile2d || !nofast);
     RAC_REQUIRE(fast || !tile2d, "rac_conv2d_fwd_split: 2-D tiles need the unrolled 3x3 form");
-    const char* nofast5 = getenv("RAC_ROWS_FAST5");  // (=0: the generic loop for 5x5 convs on maps larger than a tile)
+    // (RAC_ROWS_FAST5=0: the generic loop for 5x5 convs on maps larger than a tile; every call: the tests toggle it)
+    const bool fast5 = env_int("RAC_ROWS_FAST5", 1);
     const size_t lds5 = (size_t)2 * 2 * 4 * ((((nrows / a->W) * (a->W + 4)) + 15) & ~15) * 16;
-    if (a->ksize == 5 && width == 0 && p.tile_m == 128 && p.cps % 25 == 0 && !(nofast && atoi(nofast)) &&
-        !(nofast5 && atoi(nofast5) == 0) && lds5 <= (size_t)2 * 2 * 4 * (256 + 16) * 16) {
+    if (a->ksize == 5 && width == 0 && p.tile_m == 128 && p.cps % 25 == 0 && !nofast && fast5 && lds5 <= (size_t)ROWS_LDS_MAX) {
       fn = fast5_fns[nv - 2];
       lds_rows = lds5;
     }
@@ -3049,38 +2950,40 @@ static int conv16_launch(const rac_conv_args* a, const uint32_t* a_amax0, const 
       const int bpr = (tile2d ? 16 : a->W) / 16, mb_wave = width == 2 ? 2 : 4, bnw = width == 2 ? 32 : (width == 1 ? 64 : 128);
       const bool pool_ok = fast && p.split_k == 1 && !a->stats && !lstm_h && a->H % 2 == 0 && a->W % 16 == 0 &&
                            (bpr == 1 || bpr == 2) && mb_wave % (2 * bpr) == 0 && (p.tile_m / (16 * bpr)) % 2 == 0 &&
-                           p.M % p.tile_m == 0 && a->Cout % bnw == 0 && (long)p.M * a->Cout * 4 < (1l << 32) && RAC_EPILOGUE_FAST;
+                           p.M % p.tile_m == 0 && a->Cout % bnw == 0 && (long)p.M * a->Cout * 4 < (1l << 32);
       if (pool_query) return pool_ok ? 1 : 0;
       if (a->out1) {
         RAC_REQUIRE(pool_ok, "rac_conv2d_fwd_split: this conv cannot pool in its epilogue (rac_conv2d_fwd_split_pool_ok)");
         p.pool_out = a->out1, p.pool_bpr = bpr;
       }
     }
+    static bool rows_attr = false;
+    if (!rows_attr) {
+      for (int i = 0; i < 21; ++i) {
+        const rows_fn f = i < 9 ? fns[i / 3][i % 3] : (i < 18 ? fast_fns[(i - 9) / 3][i % 3] : fast5_fns[i - 18]);
+        if (f && raise_lds_limit(f, ROWS_LDS_MAX) != RAC_OK) return RAC_ELAUNCH;
+      }
+      rows_attr = true;
+    }
     // narrow layers (64 / 32 columns), unsplit K, many more tiles than the chip holds: persistent workgroups that walk
     // the tiles and request the next tile's first chunk under the current tile's last one
     static const rows_fn persist_fns[2][3] = {
         {conv16_rows_persist_kernel<2, 2, 1>, conv16_rows_persist_kernel<3, 2, 1>, conv16_rows_persist_kernel<4, 2, 1>},
         {conv16_rows_persist_kernel<2, 4, 1>, conv16_rows_persist_kernel<3, 4, 1>, conv16_rows_persist_kernel<4, 4, 1>}};
-    static const char* nopersist = getenv("RAC_ROWS_PERSIST");
-    static const int persist_wgs = [] { const char* e = getenv("RAC_ROWS_PERSIST_WGS"); return e ? atoi(e) : 512; }();
+    static const bool persist = env_int("RAC_ROWS_PERSIST", 1);
+    static const int persist_wgs = env_int("RAC_ROWS_PERSIST_WGS", 512);
     // (a static split of few tiles per workgroup loses to the hardware's dynamic one: measured +11 % on the 8 000-tile 32x32
     // layers, -10 % on the 32 000-tile 64x64 ones)
-    if (fast && width >= 1 && p.split_k == 1 && !(nopersist && atoi(nopersist) == 0) &&
+    if (fast && width >= 1 && p.split_k == 1 && persist &&
         ((int)grid.x >= 32 * persist_wgs || ((int)grid.x >= 4 * persist_wgs && (int)grid.x % persist_wgs == 0))) {
       static bool persist_attr = false;
       if (!persist_attr) {
-        for (int i = 0; i < 6; ++i) {
-          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(persist_fns[i / 3][i % 3]),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 4 * (256 + 16) * 16);
-          if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return RAC_ELAUNCH;
-          }
-        }
+        for (int i = 0; i < 6; ++i)
+          if (raise_lds_limit(persist_fns[i / 3][i % 3], ROWS_LDS_MAX) != RAC_OK) return RAC_ELAUNCH;
         persist_attr = true;
       }
-      static const char* nohalo = getenv("RAC_PERSIST_HALO_XCD");  // (=0: tile = workgroup id)
-      p.xcd_group = (want_xcd && persist_wgs % 8 == 0 && !(nohalo && atoi(nohalo) == 0)) ? 5 : 0;
+      static const bool halo = env_int("RAC_PERSIST_HALO_XCD", 1);  // (=0: tile = workgroup id)
+      p.xcd_group = (want_xcd && persist_wgs % 8 == 0 && halo) ? 5 : 0;
       hipLaunchKernelGGL(persist_fns[width - 1][nv - 2], dim3(persist_wgs, grid.y, 1), dim3(256), lds_rows,
                          reinterpret_cast<hipStream_t>(stream), p);
       return check_launch("rac_conv2d_fwd_split(image rows, persistent)");
@@ -3096,22 +2999,21 @@ static int conv16_launch(const rac_conv_args* a, const uint32_t* a_amax0, const 
   p.xcd_group = want_xcd && grid.x > 1 && (grid.y * grid.z) % 8 == 0;
   // many M-tiles, K unsplit: the workgroups that share an activation tile run back to back on one XCD (RAC_TILE_PAIR_XCD=0:
   // the weight-slab grouping above / hardware order)
-  static const char* pairn = getenv("RAC_TILE_PAIR_XCD");
-  const bool pair_ok = want_xcd && grid.z == 1 && grid.x >= 64 && !(pairn && atoi(pairn) == 0);
+  static const bool pair = env_int("RAC_TILE_PAIR_XCD", 1);
+  const bool pair_ok = want_xcd && grid.z == 1 && grid.x >= 64 && pair;
   if (pair_ok && p.xcd_group && grid.y % 8 == 0 && grid.y > 8) p.xcd_group = 3;
   // (Layers with 2 or 4 column tiles keep the hardware order: running an M-tile's column tiles back to back on one XCD
   // puts all their weight slabs -- 4 x 2.4 MB for the planner's 8x8 vgg layers -- through one 4 MB L2 at once: measured
   // 0.402 -> 0.433 ms on 256 -> 512.)
   size_t lds_tile = 2 * T16_ABUF;  // 36,864 B
   // waves 2 x 2 (template argument 2); the 1 x 4 arrangement of the same kernel measured 10 % slower
-  static const char* noym = getenv("RAC_TILE_YMAJOR");
-  const bool ym = a->W == 8 && p.tile_m == 2 * p.HW && !(noym && atoi(noym) == 0);  // 8x8 / 6x8 maps: skip vertical padding
+  static const bool ymajor = env_int("RAC_TILE_YMAJOR", 1);
+  const bool ym = a->W == 8 && p.tile_m == 2 * p.HW && ymajor;  // 8x8 / 6x8 maps: skip vertical padding
   typedef void (*tile_fn)(Conv16P);
   // 3x3 convs whose K ranges are whole chunks: the unrolled-tap instance (RAC_TILE_UNROLL3=0: the generic loop)
-  static const char* nou3 = getenv("RAC_TILE_UNROLL3");
-  const bool u3 = a->ksize == 3 && p.cps % 9 == 0 && !(nou3 && atoi(nou3) == 0);
-  static const char* nou5 = getenv("RAC_TILE_UNROLL5");
-  const bool u5 = a->ksize == 5 && p.cps % 25 == 0 && !(nou5 && atoi(nou5) == 0);
+  static const bool unroll3 = env_int("RAC_TILE_UNROLL3", 1), unroll5 = env_int("RAC_TILE_UNROLL5", 1);
+  const bool u3 = a->ksize == 3 && p.cps % 9 == 0 && unroll3;
+  const bool u5 = a->ksize == 5 && p.cps % 25 == 0 && unroll5;
   const tile_fn fn =
       u5 ? (p.tile_m == 128 ? (ym ? (tile_fn)conv16_tile_kernel<2, true, true, 5> : (tile_fn)conv16_tile_kernel<2, true, false, 5>)
                             : (ym ? (tile_fn)conv16_tile_kernel<2, false, true, 5> : (tile_fn)conv16_tile_kernel<2, false, false, 5>)) :
@@ -3125,14 +3027,8 @@ static int conv16_launch(const rac_conv_args* a, const uint32_t* a_amax0, const 
     if (!ym_attr) {
       for (tile_fn f : {(tile_fn)conv16_tile_kernel<2, true, true>, (tile_fn)conv16_tile_kernel<2, false, true>,
                         (tile_fn)conv16_tile_kernel<2, true, true, 3>, (tile_fn)conv16_tile_kernel<2, false, true, 3>,
-                        (tile_fn)conv16_tile_kernel<2, true, true, 5>, (tile_fn)conv16_tile_kernel<2, false, true, 5>}) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           2 * T16Y_ABUF);
-        if (e != hipSuccess) {
-          set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-          return RAC_ELAUNCH;
-        }
-      }
+                        (tile_fn)conv16_tile_kernel<2, true, true, 5>, (tile_fn)conv16_tile_kernel<2, false, true, 5>})
+        if (raise_lds_limit(f, 2 * T16Y_ABUF) != RAC_OK) return RAC_ELAUNCH;
       ym_attr = true;
     }
   }
@@ -3277,9 +3173,8 @@ extern "C" int rac_conv2d_wgrad_split(const rac_wgrad_args* a, void* stream) {
   p.presplit = a->presplit ? 1 : 0;
   RAC_REQUIRE(!p.presplit || (a->Cout % 16 == 0 && p.C0 % 8 == 0), "rac_conv2d_wgrad_split: presplit operand alignment");
   // thin 3x3 layers on large maps: all nine taps per workgroup, dy and x fetched once (wgrad16_allky_kernel)
-  static const char* noallky = getenv("RAC_WGRAD_ALLKY");
-  if (a->ksize == 3 && a->Cout <= 128 && a->H % 32 == 0 && !p.presplit && p.x1_skip == 0 && a->all_ky &&
-      !(noallky && atoi(noallky) == 0)) {
+  static const bool allky = env_int("RAC_WGRAD_ALLKY", 1);
+  if (a->ksize == 3 && a->Cout <= 128 && a->H % 32 == 0 && !p.presplit && p.x1_skip == 0 && a->all_ky && allky) {
     p.nseg = a->col_segments > 1 ? a->col_segments : 1;
     RAC_REQUIRE(a->W % p.nseg == 0 && p.nsplit <= a->T * p.G * p.nseg,
                 "rac_conv2d_wgrad_split: col_segments must divide W; nsplit <= T * groups * col_segments");
@@ -3287,12 +3182,7 @@ extern "C" int rac_conv2d_wgrad_split(const rac_wgrad_args* a, void* stream) {
     const int lds = 2 * 16384 + 4 * 40 * 256;
     static bool attr_allky = false;
     if (!attr_allky) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16_allky_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) {
-        set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return RAC_ELAUNCH;
-      }
+      if (raise_lds_limit(wgrad16_allky_kernel, lds) != RAC_OK) return RAC_ELAUNCH;
       attr_allky = true;
     }
     hipLaunchKernelGGL(wgrad16_allky_kernel, grid, dim3(256), lds, reinterpret_cast<hipStream_t>(stream), p);
@@ -3311,11 +3201,7 @@ extern "C" int rac_conv2d_wgrad_split(const rac_wgrad_args* a, void* stream) {
   const int lds = 2 * 16384 + (a->ksize + 1) * 8192;
   static bool attr_done[8] = {false, false, false, false, false, false, false, false};
   if (!attr_done[fi]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return RAC_ELAUNCH;
-    }
+    if (raise_lds_limit(fn, lds) != RAC_OK) return RAC_ELAUNCH;
     attr_done[fi] = true;
   }
   hipLaunchKernelGGL(fn, grid, dim3(256), lds, reinterpret_cast<hipStream_t>(stream), p);

@@ -1,20 +1,19 @@
 #!/bin/bash
 # Build a variant of librac_hip.so with extra compiler flags, for A/B runs on the GPU box:
-#   bash tools/build_variant.sh <name> [-DRAC_EXP_...=1 ...]   ->  robot_aware_control_amd/variants/librac_<name>.so
+#   bash tools/build_variant.sh <name> [extra hipcc flags ...]   ->  robot_aware_control_amd/variants/librac_<name>.so
 #   RAC_HIP_LIB=robot_aware_control_amd/variants/librac_<name>.so python tools/bench_gemm.py ...
-# RAC_PACKED=1 keeps the compiler's packed fp32 forms (v_pk_fma_f32 ...), which the shipped library is built without.
+# Every csrc/*.hip is compiled with the Makefile's own compiler and flags plus the extra ones: the variant has every export.
 set -eo pipefail
 name=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd)
-nopk="-Xclang -target-feature -Xclang -packed-fp32-ops"; [ "$RAC_PACKED" = "1" ] && nopk=""
-obj=/tmp/rac_variant_$name; mkdir -p "$obj" "$root/robot_aware_control_amd/variants"
-# RAC_PACKED_FILES="rac_frame rac_split16": packed fp32 ops in those translation units only (bisecting the miscompute)
-for f in rac_igemm rac_split16 rac_pointwise rac_frame; do
-  fl=$nopk; case " $RAC_PACKED_FILES " in *" $f "*) fl="";; esac
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I"$root/include" -Wall -Wno-unused-function \
-    $fl "$@" \
-    -c "$root/robot_aware_control_amd/csrc/$f.hip" -o "$obj/$f.o" &
+csrc=$root/robot_aware_control_amd/csrc
+cc=$(make -s --no-print-directory -C "$csrc" --eval='print-cc: ; @echo $(HIPCC) $(CXXFLAGS)' print-cc)
+obj=$(mktemp -d "/tmp/rac_variant_$name.XXXXXX"); mkdir -p "$root/robot_aware_control_amd/variants"
+pids=()
+for src in "$csrc"/*.hip; do
+  $cc "$@" -c "$src" -o "$obj/$(basename "$src" .hip).o" &
+  pids+=($!)
 done
-wait
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 "$obj"/*.o -o "$root/robot_aware_control_amd/variants/librac_$name.so"
+for pid in "${pids[@]}"; do wait "$pid"; done
+${cc%% *} -shared -fPIC --offload-arch=gfx950 "$obj"/*.o -o "$root/robot_aware_control_amd/variants/librac_$name.so"
 echo "built variants/librac_$name.so"
