@@ -567,6 +567,21 @@ int rac_psnr_ssim(const float* a, const float* b, const float* mask, float* sq_e
 int rac_eval_frames(int32_t kind, const float* pred, const float* target, const float* mask, float robot_weight,
                     float* rows, int32_t S, int32_t B, int32_t H, int32_t W, void* stream);
 
+/* Copy-baseline world error of whole videos (measure_obj_movement.py:21-32: CopyModel, dynamics.py:341-357, scored by
+ * world_mse_criterion, losses.py:66-78), for V videos of T frames:
+ *   step_err[v][t-1] = sum_{c, p : mask(v,t)[p] == 0} (img(v,t)[c][p] - img(v,t-1)[c][p])^2 / (3 #{p : mask(v,t)[p] == 0} + 1),  t = 1..T-1
+ *   score[v]         = step_err[v][0] + step_err[v][1] + ... in that order (fp32, as the reference's running `+=`)
+ * frame (v,t) = images + v*img_video_stride + t*img_frame_stride, a dense [3][H][W] plane set; mask (v,t) likewise, [H][W];
+ * strides in elements, so (T,B,...) and (B,T,...) batches and windows of them are read in place.
+ * A robot pixel is mask != 0 (`mask.type(torch.bool)`).
+ * step_err [V][T-1] and score [V] are OVERWRITTEN: nothing needs zeroing on entry.  No atomics; every sum runs in one
+ * fixed order: the bits of score[v] and step_err[v][:] depend only on that video's frames and masks and on (T, H, W),
+ * not on V, the video's position, the strides (16-byte loads are used when H W, all four strides and both bases allow
+ * them, scalar loads otherwise: the same sums in the same order) or the run. */
+int rac_video_movement(const float* images, int64_t img_video_stride, int64_t img_frame_stride, const float* masks,
+                       int64_t mask_video_stride, int64_t mask_frame_stride, float* step_err, float* score,
+                       int32_t V, int32_t T, int32_t H, int32_t W, void* stream);
+
 /* CEM step tail (trajectory_sampler.py:149-169 + losses.py:224-263), fused:
  *   next = (1-m)*curr + m*rgb; next *= (1-next_mask) if next_mask;
  *   cost = -sqrt(sum (255*(next-goal))^2) [dontcare: robot|goal-mask pixels dropped, / #world pixels]

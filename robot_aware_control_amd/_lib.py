@@ -167,6 +167,7 @@ _SIGS = {
     "rac_kl_bwd": [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
     "rac_psnr_ssim": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "rac_eval_frames": [i32, vp, vp, vp, f32, vp, i32, i32, i32, i32, vp],
+    "rac_video_movement": [vp, i64, i64, vp, i64, i64, vp, vp, i32, i32, i32, i32, vp],
     "rac_cem_step_tail": [vp, vp, vp, vp, vp, vp, i32, f32, i32, vp, vp, i32, i32, vp],
     "rac_cem_robot_inputs": [vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp, vp, i32, i32, i32, i32, i32, vp],
     "rac_adam_step": [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, vp],

@@ -1136,4 +1136,117 @@ extern "C" int rac_eval_frames(int32_t kind, const float* pred, const float* tar
   return check_launch("rac_eval_frames");
 }
 
+// ---- the copy baseline's world error of whole videos (measure_obj_movement.py), one call per batch ---------------
+namespace rac {
+
+constexpr int MV_THREADS = 256;
+
+// grid V (T - 1), 256 threads: workgroup (v, k) scores frame k + 1 of video v against frame k and nothing else, so no
+// value crosses a workgroup.  The frame is walked in groups of four adjacent pixels ("quads"): thread i takes quads
+// i, i + 256, ... and adds, per quad, channel 0's four squared differences, then channel 1's, then channel 2's, each
+// with one fma into its one running sum.  VEC reads a quad with 16-byte loads (7 per quad: two frames x three planes
+// and the mask), the other form with scalar loads and a bounds test per pixel (HW % 4 != 0, a stride that is no
+// multiple of 4 floats, a base off 16 bytes); a pixel's quad, thread and place in the order do not depend on the
+// form, so both give the same bits.  Then the xor butterfly inside each wave and the four wave partials added
+// serially, wave 0 first.  The world count is an integer.
+template <bool VEC>
+__global__ void __launch_bounds__(MV_THREADS) video_movement_kernel(const float* images, long ivs, long ifs,
+                                                                    const float* masks, long mvs, long mfs,
+                                                                    float* step_err, int steps, int HW) {
+  __shared__ float sh_s[MV_THREADS / 64];
+  __shared__ int sh_n[MV_THREADS / 64];
+  const int v = blockIdx.x / steps, k = blockIdx.x - v * steps;
+  const float* prev = images + (long)v * ivs + (long)k * ifs;
+  const float* cur = prev + ifs;
+  const float* mk = masks + (long)v * mvs + (long)(k + 1) * mfs;
+  const int quads = (HW + 3) >> 2;
+  float s = 0.f;
+  int n = 0;
+  for (int q = threadIdx.x; q < quads; q += MV_THREADS) {
+    const int p0 = q * 4;
+    float m[4], a[3][4], b[3][4];
+    if (VEC) {
+      const f32x4 m4 = *reinterpret_cast<const f32x4*>(mk + p0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) m[j] = m4[j];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const f32x4 a4 = *reinterpret_cast<const f32x4*>(cur + (long)c * HW + p0);
+        const f32x4 b4 = *reinterpret_cast<const f32x4*>(prev + (long)c * HW + p0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[c][j] = a4[j], b[c][j] = b4[j];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool in = p0 + j < HW;  // a pixel past the frame counts as a robot pixel: it adds nothing
+        m[j] = in ? mk[p0 + j] : 1.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          a[c][j] = in ? cur[(long)c * HW + p0 + j] : 0.f;
+          b[c][j] = in ? prev[(long)c * HW + p0 + j] : 0.f;
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) n += m[j] == 0.f ? 1 : 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float d = a[c][j] - b[c][j];
+        s = m[j] == 0.f ? __builtin_fmaf(d, d, s) : s;
+      }
+  }
+  s = wave_sum(s);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  if ((threadIdx.x & 63) == 0) sh_s[threadIdx.x >> 6] = s, sh_n[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = sh_s[0];
+    int world = sh_n[0];
+#pragma unroll
+    for (int w = 1; w < MV_THREADS / 64; ++w) t += sh_s[w], world += sh_n[w];
+    step_err[blockIdx.x] = t / (float)(3 * world + 1);
+  }
+}
+
+// one thread per video: the reference's running `+=` over the steps, step 0 first
+__global__ void video_score_kernel(const float* step_err, float* score, int V, int steps) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  const float* e = step_err + (long)v * steps;
+  float t = e[0];
+  for (int k = 1; k < steps; ++k) t += e[k];
+  score[v] = t;
+}
+
+}  // namespace rac
+
+extern "C" int rac_video_movement(const float* images, int64_t img_video_stride, int64_t img_frame_stride,
+                                  const float* masks, int64_t mask_video_stride, int64_t mask_frame_stride,
+                                  float* step_err, float* score, int32_t V, int32_t T, int32_t H, int32_t W,
+                                  void* stream) {
+  using namespace rac;
+  RAC_REQUIRE(images && masks && step_err && score && V >= 1 && T >= 2 && H >= 1 && W >= 1 && img_video_stride >= 0 &&
+                  img_frame_stride >= 0 && mask_video_stride >= 0 && mask_frame_stride >= 0,
+              "rac_video_movement: bad args");
+  RAC_REQUIRE((long)H * W < (1L << 29) && (long)V * (T - 1) < (1L << 31), "rac_video_movement: too many pixels or steps");
+  const int HW = H * W, steps = T - 1;
+  const bool vec = HW % 4 == 0 && img_video_stride % 4 == 0 && img_frame_stride % 4 == 0 && mask_video_stride % 4 == 0 &&
+                   mask_frame_stride % 4 == 0 && aligned16(images) && aligned16(masks);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (vec)
+    hipLaunchKernelGGL(video_movement_kernel<true>, dim3(V * steps), dim3(MV_THREADS), 0, st, images, img_video_stride,
+                       img_frame_stride, masks, mask_video_stride, mask_frame_stride, step_err, steps, HW);
+  else
+    hipLaunchKernelGGL(video_movement_kernel<false>, dim3(V * steps), dim3(MV_THREADS), 0, st, images, img_video_stride,
+                       img_frame_stride, masks, mask_video_stride, mask_frame_stride, step_err, steps, HW);
+  const int rc = check_launch("rac_video_movement");
+  if (rc != RAC_OK) return rc;
+  hipLaunchKernelGGL(video_score_kernel, dim3(cdiv(V, 64)), dim3(64), 0, st, step_err, score, V, steps);
+  return check_launch("rac_video_movement (score)");
+}
+
 RAC_DEVICE_CODE_END

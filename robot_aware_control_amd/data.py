@@ -483,7 +483,8 @@ class RoboNetDataset(data.Dataset):
 # --------------------------------------------------------------------------- #
 # loaders (robonet_dataloaders.py:21-80, 137-199)
 # --------------------------------------------------------------------------- #
-def _robot_files(config, subdir, train_dirs, label):
+def _robot_files(config, subdir, train_dirs, label, keep=None):
+    """`keep(folder_name, path)`: an optional predicate on the discovered files (`create_movement_loader`)."""
     files, labels = [], []
     data_path = os.path.join(config.data_root, subdir)
     if not os.path.isdir(data_path):
@@ -491,7 +492,8 @@ def _robot_files(config, subdir, train_dirs, label):
     for folder in os.scandir(data_path):
         if folder.is_dir() and folder.name in train_dirs:
             for d in os.scandir(folder.path):
-                if d.is_file() and d.path.lower().endswith(TRAJ_EXTENSIONS):
+                if (d.is_file() and d.path.lower().endswith(TRAJ_EXTENSIONS)
+                        and (keep is None or keep(folder.name, d.path))):
                     files.append(d.path)
                     labels.append(f"{label}_{folder.name}")
     fl = sorted(zip(files, labels), key=lambda x: x[0])
@@ -660,6 +662,48 @@ def _plain_loader(ds, config, batch_size):
     return data.DataLoader(ds, num_workers=config.data_threads, batch_size=batch_size, shuffle=True, drop_last=False,
                            pin_memory=True, generator=torch.Generator().manual_seed(config.seed), collate_fn=collate,
                            persistent_workers=config.data_threads > 0)
+
+
+MOVEMENT_FILE = "obj_movement.pkl"  # per viewpoint folder: {file path: high-movement flag}, written by movement.py
+
+
+def load_movement_table(folder_path):
+    """The table of one viewpoint folder; a folder that has not been scored names the command that scores it."""
+    path = os.path.join(folder_path, MOVEMENT_FILE)
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{path} not found: score the folder's videos first with "
+                                f"`python -m src.prediction.measure_obj_movement --data_root ...`")
+    with open(path, "rb") as f:
+        return pickle.load(f)
+
+
+def _movement_files(config, subdir, train_dirs, label):
+    """`_robot_files` restricted to the files whose table entry is true (robonet_dataloaders.py:210-292)."""
+    data_path = os.path.join(config.data_root, subdir)
+    if not os.path.isdir(data_path):
+        return []
+    tables = {f.name: load_movement_table(f.path) for f in os.scandir(data_path) if f.is_dir() and f.name in train_dirs}
+    return _robot_files(config, subdir, train_dirs, label, keep=lambda name, path: bool(tables[name].get(path, False)))
+
+
+def movement_files(config, n_files: int = 4000):
+    """(files, labels) of `create_movement_loader`: per robot the flagged files sorted by path and shuffled after
+    `random.seed(config.seed)`, baxter + widowx + sawyer concatenated, reseeded and shuffled again, the first `n_files`."""
+    fl = (_movement_files(config, "baxter_views", BAXTER_TRAIN_DIRS, "baxter")
+          + _movement_files(config, "widowx_views", WIDOWX_TRAIN_DIRS, "widowx")
+          + _movement_files(config, "sawyer_views", SAWYER_TRAIN_DIRS, "sawyer"))
+    random.seed(config.seed)
+    random.shuffle(fl)
+    fl = fl[:n_files]
+    return [x[0] for x in fl], [x[1] for x in fl]
+
+
+def create_movement_loader(config, n_files: int = 4000):
+    """Loader over the high-movement videos only (robonet_dataloaders.py:295-327): up to 4000 files flagged true in
+    their viewpoint folder's obj_movement.pkl, no augmentation, batches of `config.batch_size`."""
+    files, labels = movement_files(config, n_files)
+    ds = RoboNetDataset(files, labels, config, device_images=getattr(config, "device_images", False))
+    return _plain_loader(ds, config, config.batch_size)
 
 
 def create_transfer_loader(config, n_files: int = 400):

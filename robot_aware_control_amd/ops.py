@@ -3176,6 +3176,34 @@ def eval_frames(pred, target, mask, kind: int, robot_weight: float, S: int = 1, 
     return rows
 
 
+def video_movement(images, masks, time_first: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The copy baseline's world error of whole videos in one call (`rac_video_movement`, what
+    measure_obj_movement.py:21-32 sums per video): `images` (T, B, 3, H, W) and `masks` (T, B, 1, H, W), or (B, T, ...)
+    with `time_first=False`, or slices of such batches along T or B -- the strides are handed over and nothing is
+    copied while every frame is dense (`.contiguous()` only otherwise).  Returns `score` (B,), the sum over the steps
+    of `step_err` (T - 1, B), the world mse of frame t against frame t - 1 of that video alone."""
+    _require_cuda(images)
+    _require_cuda(masks)
+    if images.dim() != 5 or masks.dim() != 5:
+        raise _lib.RacError(f"video_movement: 5-d batches, got {tuple(images.shape)} and {tuple(masks.shape)}")
+    if not time_first:
+        images, masks = images.transpose(0, 1), masks.transpose(0, 1)
+    T, B, Cc, H, W = images.shape
+    if Cc != 3 or tuple(masks.shape) != (T, B, 1, H, W) or B < 1:
+        raise _lib.RacError(f"video_movement: (T,B,3,H,W) frames and (T,B,1,H,W) masks, got {tuple(images.shape)} and "
+                            f"{tuple(masks.shape)}")
+    images, masks = images.detach().to(torch.float32), masks.detach().to(torch.float32)
+    if T and not images[0, 0].is_contiguous():
+        images = images.contiguous()
+    if T and not masks[0, 0].is_contiguous():
+        masks = masks.contiguous()
+    step = torch.empty((B, max(T - 1, 0)), device=images.device, dtype=torch.float32)
+    score = torch.empty((B,), device=images.device, dtype=torch.float32)
+    call("rac_video_movement", ptr(images), images.stride(1), images.stride(0), ptr(masks), masks.stride(1),
+         masks.stride(0), ptr(step), ptr(score), B, T, H, W, stream_ptr())
+    return score, step.t()
+
+
 class ZeroRegion(torch.autograd.Function):
     """zero_robot_region (src/utils/image.py:5-19), out of place."""
 
