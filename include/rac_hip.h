@@ -582,6 +582,37 @@ int rac_video_movement(const float* images, int64_t img_video_stride, int64_t im
                        int64_t mask_video_stride, int64_t mask_frame_stride, float* step_err, float* score,
                        int32_t V, int32_t T, int32_t H, int32_t W, void* stream);
 
+/* End-effector heatmaps of T x B frames in one launch (robonet_dataset.py:482-544 create_heatmaps, :420-431
+ * get_2d_eef_pos; called per video from trainer.py:234-246 and locobot_model.py:179-193).  For frame (t, b), with
+ * s = states + t*state_frame_stride + b*state_video_stride (>= 3 floats, normalised world-frame position),
+ * lo = low + b*bound_stride, hi = high + b*bound_stride (>= 3 floats each) and v = views[b]:
+ *   fp32:  p[k] = s[k] * (hi[k] - lo[k]) + lo[k]  (k = 0..2; multiply and add rounded separately, never an fma);
+ *          p[2] += v.z_offset
+ *   fp64:  pix = v.proj (3x4, row-major) * [p; 1], each row summed left to right, products and sums rounded separately;
+ *          x = pix[0] / pix[2] * v.scale_x,  y = pix[1] / pix[2] * v.scale_y     (no depth test, as the reference)
+ *   mx = trunc(x), my = trunc(y);  valid = 0 <= mx < W && 0 <= my < H, decided on the fp64 values (x > -1 && x < W ...),
+ *          so a NaN / infinite coordinate is invalid and nothing is cast out of range
+ *   heat[yy][xx] = 100 / (2 pi 25) * exp(-((xx - mx)^2 + (yy - my)^2) / 50) in fp32 for a valid frame, all zeros otherwise
+ * written to heatmaps + t*out_frame_stride + b*out_video_stride as a dense [H][W] plane.  All strides in elements: states
+ * (T,B,S) and (B,T,S) are read in place, and rows 1..T of a (T+1,B,1,H,W) tensor are written by passing its row 1.
+ * views: B records in DEVICE memory (8-byte aligned), built by the host in fp64: proj = K @ wTc[:3], scale = target size /
+ * the camera's original size, z_offset the robot's gripper offset.  rac_heatmap_view_bytes() = sizeof(rac_heatmap_view).
+ * centres: NULL, or int32 [T][B][3] = (mx, my, valid); for an invalid frame mx / my are the truncated coordinates
+ * saturated to int32 (0 where not finite).  Any 1 <= H, W <= 2048 (16-byte stores when W % 4 == 0 and the output strides
+ * and base allow them, scalar stores otherwise: the same values).  One workgroup per frame, no atomics: a frame's bits
+ * depend on its own state, bounds, view and (H, W) alone. */
+typedef struct rac_heatmap_view {
+  double proj[12];
+  double scale_x, scale_y;
+  float z_offset;
+  int32_t reserved;
+} rac_heatmap_view;
+int rac_heatmap_view_bytes(void);
+int rac_eef_heatmaps(const float* states, int64_t state_frame_stride, int64_t state_video_stride, const float* low,
+                     const float* high, int64_t bound_stride, const rac_heatmap_view* views, float* heatmaps,
+                     int64_t out_frame_stride, int64_t out_video_stride, int32_t* centres, int32_t T, int32_t B, int32_t H,
+                     int32_t W, void* stream);
+
 /* CEM step tail (trajectory_sampler.py:149-169 + losses.py:224-263), fused:
  *   next = (1-m)*curr + m*rgb; next *= (1-next_mask) if next_mask;
  *   cost = -sqrt(sum (255*(next-goal))^2) [dontcare: robot|goal-mask pixels dropped, / #world pixels]

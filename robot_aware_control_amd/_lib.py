@@ -69,6 +69,12 @@ class ImageJob(C.Structure):
                 ("factor", C.c_double * 4)]
 
 
+class HeatmapView(C.Structure):
+    """struct rac_heatmap_view (include/rac_hip.h): one video's camera of a rac_eef_heatmaps launch."""
+    _fields_ = [("proj", C.c_double * 12), ("scale_x", C.c_double), ("scale_y", C.c_double), ("z_offset", f32),
+                ("reserved", i32)]
+
+
 OPTIM_RMSPROP, OPTIM_SGD = 0, 1            # RAC_OPTIM_* rules
 OPTIM_NESTEROV, OPTIM_FIRST_STEP = 1, 2    # RAC_OPTIM_* flags
 
@@ -168,6 +174,8 @@ _SIGS = {
     "rac_psnr_ssim": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "rac_eval_frames": [i32, vp, vp, vp, f32, vp, i32, i32, i32, i32, vp],
     "rac_video_movement": [vp, i64, i64, vp, i64, i64, vp, vp, i32, i32, i32, i32, vp],
+    "rac_heatmap_view_bytes": [],
+    "rac_eef_heatmaps": [vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i32, i32, i32, i32, vp],
     "rac_cem_step_tail": [vp, vp, vp, vp, vp, vp, i32, f32, i32, vp, vp, i32, i32, vp],
     "rac_cem_robot_inputs": [vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp, vp, i32, i32, i32, i32, i32, vp],
     "rac_adam_step": [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, vp],

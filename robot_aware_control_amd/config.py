@@ -110,7 +110,10 @@ _NATIVE = [("ddp_bucket_mb", I, 64), ("cem_shard", B, True),
            ("ddp_shard_optimizer", B, False),  # DDP: reduce-scatter + Adam on 1/world slices + parameter all-gather
            ("plot", B, False),          # write the per-epoch generation GIFs of PredictionTrainer.plot
            # _eval_video: three prior samples per window, the best by autoreg_psnr (svg, finetune*, autoregressive)
-           ("eval_best_of_three", B, False)]
+           ("eval_best_of_three", B, False),
+           # --model_use_heatmap: an .npz of camera matrices (heatmaps.CameraTable.save, tools/export_camera_calibration.py);
+           # None: the reference checkout's src/utils/camera_calibration.py
+           ("camera_calibration", S, None)]
 
 
 def _add(parser, table):

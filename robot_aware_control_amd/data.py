@@ -17,7 +17,10 @@ What is different, for a trainer that consumes ~2 800 frames/s per GPU:
   * `--device_images True` (off by default) moves the image half of an item to the GPU: the dataset hands over the raw
     uint8 frames, the binary raw masks and the augmentation parameters it drew (`draw_image_params`), `collate` packs a
     batch's videos (of any raw sizes) into one flat uint8 buffer plus one `rac_image_job` per video, and one
-    `rac_image_pipeline` launch on the prefetcher's stream writes the time-first fp32 `images` / `masks`.
+    `rac_image_pipeline` launch on the prefetcher's stream writes the time-first fp32 `images` / `masks`;
+  * `--model_use_heatmap True`: an item carries its bounds and its camera (`heatmap_view`, a row of numbers from
+    heatmaps.CameraTable) and `process_batch` / the prefetcher add the time-first `heatmaps` of the whole batch with one
+    `rac_eef_heatmaps` launch on the stream they already use (the reference's dataset raises under this flag).
 """
 from __future__ import annotations
 
@@ -365,7 +368,8 @@ class ImagePipeline:
 class RoboNetDataset(data.Dataset):
     """Trajectory files -> the reference's item dict (robonet_dataset.py:23-171): images (T,3,h,w) in [0,1], states (T,R)
     normalised, actions (T-1,A), masks (T,1,h,w) in {0,1}, qpos (T,Q), robot, folder, file_path, idx (+ low / high /
-    raw_* for finetune_* experiments, high_movement with --load_movement_info).
+    raw_* for finetune_* experiments, high_movement with --load_movement_info; low / high / heatmap_view with
+    --model_use_heatmap, from which `process_batch` makes the batch's `heatmaps` on the device).
 
     `device_images=True`: instead of `images` / `masks` an item carries what the device needs to make them
     (`rac_image_pipeline`, through `collate` and `process_batch` / the prefetcher): `frames` uint8 (T,Hs,Ws,3) as
@@ -388,6 +392,8 @@ class RoboNetDataset(data.Dataset):
         # window starts: the reference's RandomState(config.seed); data-parallel ranks pass their own seed
         self._rng = np.random.RandomState(config.seed if rng_seed is None else rng_seed)
         self._movement = self._movement_tables() if config.load_movement_info else None
+        self._heatmaps = bool(getattr(config, "model_use_heatmap", False))
+        self._camera_table = None  # heatmaps.CameraTable, read on the first item under --model_use_heatmap
         self._memory = {}
         if getattr(config, "preload_ram", False):
             self._memory = {i: self[i] for i in range(len(self))}
@@ -408,6 +414,12 @@ class RoboNetDataset(data.Dataset):
         if pipe is None:
             pipe = self._pipelines[viewpoint] = NumericPipeline(viewpoint, self._config.preprocess_action)
         return pipe
+
+    def camera_table(self):
+        if self._camera_table is None:
+            from .heatmaps import CameraTable
+            self._camera_table = CameraTable.from_config(self._config)
+        return self._camera_table
 
     def _window(self, length: int, path: str):
         assert length >= self._video_length, f"{length}, {path}"
@@ -450,8 +462,11 @@ class RoboNetDataset(data.Dataset):
             robot = robot.decode() if isinstance(robot, bytes) else str(robot)
         if not len(frames) == len(raw_states) == len(raw_actions) + 1 == len(masks):
             raise AssertionError(f"{path}, {frames.shape}, {raw_states.shape}, {raw_actions.shape}, {masks.shape}")
-        if getattr(cf, "model_use_heatmap", False):
-            raise NotImplementedError  # as the reference (robonet_dataset.py:130-133)
+        if self._heatmaps and pipe.camera:
+            # the heatmap projects WORLD-frame positions; the camera strategies normalise the states in the camera frame
+            # (the reference's own open TODO, robonet_dataset.py:132-135 "need to account for camera space state")
+            raise NotImplementedError(f"model_use_heatmap with preprocess_action={cf.preprocess_action!r}: the states are "
+                                      f"in the camera frame, the heatmap needs them in the world frame")
         low, high = pipe.bounds(raw_low, raw_high)
         if self._device_images:
             if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[-1] != 3:
@@ -466,6 +481,9 @@ class RoboNetDataset(data.Dataset):
         folder = os.path.basename(os.path.dirname(name))
         item = {**pictures, "states": states, "actions": actions, **mask_keys, "robot": robot, "folder": folder,
                 "file_path": path, "idx": idx, "qpos": qpos}
+        if self._heatmaps:  # what rac_eef_heatmaps needs of this video: its bounds and its camera
+            item["low"], item["high"] = low, high
+            item["heatmap_view"] = self.camera_table().view_row(robot, folder, cf.image_height, cf.image_width).copy()
         if "finetune" in cf.experiment:  # the robot model of finetune_* windows needs the bounds (:148-166)
             item["low"], item["high"] = low, high
             if cf.preprocess_action != "raw":
@@ -757,7 +775,24 @@ def process_batch(data: dict, device) -> dict:
         if k in data:
             data[k] = data[k].transpose_(1, 0).to(device, non_blocking=True)
     data.update(pictures)
+    if HEATMAP_VIEW_KEY in data:
+        if torch.device(device).type != "cuda":
+            raise _lib.RacError("model_use_heatmap: the heatmaps are made on the GPU (rac_eef_heatmaps; no CPU fallback)")
+        with torch.cuda.device(device):
+            data["heatmaps"] = device_heatmaps(data)
     return data
+
+
+HEATMAP_VIEW_KEY = "heatmap_view"
+
+
+def device_heatmaps(batch: dict, keep=None):
+    """The time-first `heatmaps` (T, B, 1, H, W) of a `--model_use_heatmap` batch whose `states` are already time-first
+    on the GPU: one `rac_eef_heatmaps` launch on the current stream.  Removes the batch's `heatmap_view`."""
+    from .heatmaps import heatmaps_from_views
+    rows = batch.pop(HEATMAP_VIEW_KEY).numpy()
+    return heatmaps_from_views(batch["states"], batch["low"], batch["high"], rows, int(rows[0, 15]), int(rows[0, 16]),
+                               keep=keep)
 
 
 class DevicePrefetcher:
@@ -787,6 +822,10 @@ class DevicePrefetcher:
                     t = out[k]
                     t = t if t.is_pinned() else t.pin_memory()
                     out[k] = t.to(self.device, non_blocking=True).transpose(0, 1).contiguous()
+            if HEATMAP_VIEW_KEY in out:  # one launch behind the states' upload, on this stream
+                held = []
+                out["heatmaps"] = device_heatmaps(out, keep=held)
+                raw = (raw, held)
             ev = torch.cuda.Event()
             ev.record(self.stream)
         if raw is not None:  # keep what the launch reads until the event says it has run

@@ -36,14 +36,18 @@ WORKSPACE_HIGH = (0.55, 0.3, 0.4, 1.0, 1.0)
 
 class AtlasRobotModel:
     def __init__(self, atlas: torch.Tensor, x0: float, y0: float, dx: float, dy: float, push_height: float,
-                 frame_diff=(0.0, 0.0), device=None, preprocess_action: str = "raw", exact=None):
+                 frame_diff=(0.0, 0.0), device=None, preprocess_action: str = "raw", exact=None, config=None,
+                 camera_table=None):
         """atlas: uint8 / bool (ny, nx, H, W), node (i, j) rendered with the end effector at (x0 + i dx, y0 + j dy) in
         the frame of the (de-normalised) states handed to `predict_batch`; `frame_diff`: offset of the robot's own
         frame, subtracted before and added after the propagation as the reference does (LOCO_WX250S_DIFF, ...).
         `preprocess_action`: the config's strategy -- anything but "raw" makes `predict_batch` read the world-frame
         `raw_actions / raw_states / raw_low / raw_high` of the batch, as the analytical models do
         (locobot_model.py:113-127).  `exact`: the model the atlas was rendered from (kept by `build`): the planner can
-        re-roll its final elites with exactly rendered masks (TrajectorySampler, `cem_exact_elites`)."""
+        re-roll its final elites with exactly rendered masks (TrajectorySampler, `cem_exact_elites`).
+        `config`: with `model_use_heatmap` set, `predict_batch` on a batch that carries `heatmaps` returns them as a third
+        tensor, rows 1..T rebuilt from the propagated states (locobot_model.py:179-193); `camera_table`: the
+        heatmaps.CameraTable for that (None: read per the config on first use)."""
         dev = torch.device(device if device is not None else "cuda")
         if dev.type != "cuda":
             raise _lib.RacError("AtlasRobotModel runs on the GPU (no CPU fallback)")
@@ -55,6 +59,7 @@ class AtlasRobotModel:
         self.device = dev
         self.preprocess_action = preprocess_action
         self.exact = exact
+        self.config, self.camera_table = config, camera_table
         self.shared_start_mask = None  # set by predict_batch: do all samples of the last batch share row 0?
 
     # ------------------------------------------------------------------ build / cache
@@ -107,7 +112,9 @@ class AtlasRobotModel:
         displacements, low / high (N, 5) -- with a non-"raw" `preprocess_action` the batch's `raw_*` entries instead
         (world-frame actions and states, the file's own bounds).  Every sample is propagated from ITS start with ITS
         bounds (a planner's candidates share them; the windows of a training batch do not).  Returns device tensors
-        (states (T+1, N, 5) normalised, masks (T+1, N, 1, H, W) in {0, 1})."""
+        (states (T+1, N, 5) normalised, masks (T+1, N, 1, H, W) in {0, 1}) -- and, when the config has
+        `model_use_heatmap` and the batch carries `heatmaps`, those with rows 1..T rebuilt from the returned states
+        (world-frame, de-normalised by the bounds they were normalised with) as a third tensor."""
         dev = self.device
         pre = "" if self.preprocess_action == "raw" else "raw_"
         if pre and any(pre + k not in data for k in ("actions", "states", "low", "high")):
@@ -134,4 +141,7 @@ class AtlasRobotModel:
         _lib.call("rac_cem_robot_inputs", actions.data_ptr(), start.data_ptr(), low.data_ptr(), high.data_ptr(),
                   self.atlas.data_ptr(), self.nx, self.ny, self.x0, self.y0, self.dx, self.dy, self.diff[0], self.diff[1],
                   self.push_height, states.data_ptr(), masks.data_ptr(), T, N, A, self.H * self.W, 1, _lib.stream_ptr())
+        if getattr(self.config, "model_use_heatmap", False) and "heatmaps" in data:
+            from .robot_model import rebuilt_heatmaps
+            return states, masks, rebuilt_heatmaps(self, self.config, data, states, T, (pre + "low", pre + "high"))
         return states, masks

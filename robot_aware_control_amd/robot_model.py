@@ -207,10 +207,11 @@ class LearnedRobotModel:
     """`PredictionTrainer.robot_model` over the two learned predictors.  `renderers`: {viewpoint: object with the reference
     mask envs' `generate_masks(list_of_qpos) -> list of (H, W) arrays`}, looked up by `batch["folder"]`."""
 
-    def __init__(self, config, joint_model, gripper_model, renderers=None):
+    def __init__(self, config, joint_model, gripper_model, renderers=None, camera_table=None):
         self._config = config
         self.joint_model, self.gripper_model = joint_model, gripper_model
         self.renderers = dict(renderers or {})
+        self.camera_table = camera_table  # heatmaps.CameraTable; None: read per the config on first use
 
     def rollout(self, qpos0, state0, actions):
         """qpos[t+1] = qpos[t] + joint(qpos[t], a[t]) and states[t+1] = states[t] + gripper(states[t], a[t]) for the T
@@ -235,11 +236,15 @@ class LearnedRobotModel:
     def predict_batch(self, batch):
         """The reference's `_generate_learned_robot_states` (trainer.py:164-257): (states, masks) shaped like the batch's,
         row 0 the ground truth, rows 1..T the models' rollout from row 0 over the window's actions (`raw_actions` when
-        `preprocess_action != "raw"`) and the render of every predicted joint position from its sample's viewpoint."""
+        `preprocess_action != "raw"`) and the render of every predicted joint position from its sample's viewpoint.
+        With `model_use_heatmap` a third tensor: the batch's `heatmaps` with rows 1..T rebuilt from the predicted states
+        (trainer.py:234-256), each sample with its own `low` / `high` / `robot` / `folder`, in one launch."""
         cf = self._config
-        if getattr(cf, "model_use_heatmap", False):
-            raise NotImplementedError("model_use_heatmap with the learned robot model: the reference rebuilds the heatmaps "
-                                      "from the predicted states (create_heatmaps, trainer.py:234-256), which is not built")
+        use_heatmap = bool(getattr(cf, "model_use_heatmap", False))
+        if use_heatmap and "heatmaps" not in batch:
+            raise NotImplementedError("model_use_heatmap with the learned robot model: the batch carries no `heatmaps` "
+                                      "to keep row 0 of (the heatmap rows 1..T are rebuilt from the predicted states, "
+                                      "trainer.py:234-256)")
         states, mask, qpos = batch["states"], batch["masks"], batch["qpos"]
         ac = batch["actions"] if getattr(cf, "preprocess_action", "raw") == "raw" else batch["raw_actions"]
         folders = list(batch["folder"])
@@ -261,4 +266,20 @@ class LearnedRobotModel:
                 rendered = envs[vp].generate_masks([q_host[t, b] for t in range(T)])
                 host[:, b, 0] = resize_masks(rendered, h, w)
             pred_masks[1:T + 1] = torch.from_numpy(host).to(dev).to(mask.dtype)  # the one upload
+        if use_heatmap:
+            return pred_states, pred_masks, rebuilt_heatmaps(self, cf, batch, pred_states, T)
         return pred_states, pred_masks
+
+
+def rebuilt_heatmaps(model, config, batch, pred_states, T: int, bounds=("low", "high")):
+    """A clone of `batch["heatmaps"]` with rows 1..T made from `pred_states[1:T + 1]` (trainer.py:234-246,
+    locobot_model.py:179-193); `model.camera_table` is read per the config on first use."""
+    from .heatmaps import CameraTable, batch_heatmaps
+    if model.camera_table is None:
+        model.camera_table = CameraTable.from_config(config)
+    heat = batch["heatmaps"]
+    heat = torch.as_tensor(heat).to(pred_states.device, torch.float32).clone().contiguous()
+    if T:
+        batch_heatmaps(pred_states[1:T + 1], batch[bounds[0]], batch[bounds[1]], list(batch["robot"]),
+                       list(batch["folder"]), model.camera_table, heat.shape[-2], heat.shape[-1], out=heat, first_row=1)
+    return heat
