@@ -623,6 +623,26 @@ int rac_cem_step_tail(const float* x4, const float* curr, const float* next_mask
                       const float* cost_mask, const uint8_t* goal_mask, int32_t kind, float weight, int32_t add_cost,
                       float* next_out, double* sum_cost, int32_t N, int32_t HW, void* stream);
 
+/* Also added within version 12.  The planner's --debug_cem output (src/cem/cem.py:128-178, src/cem/push/cem.py:183-239)
+ * from predicted frames that stayed on the device, one launch.
+ * Input: candidate c at step t is the planar (3, H, W) fp32 image at frames + t*step_stride + c*cand_stride (strides in
+ * elements: the caller passes rac_cem_step_tail's next_out of every step as slices of one (T, n, 3, H, W) store).
+ * rows: int32 [R] in DEVICE memory, rows[r] = the candidate shown in row block r; any order, repeats allowed.  The call
+ * cannot inspect it: the CALLER checks 0 <= rows[r] < n.
+ *   obs   (NULL or fp32 (R, T, 3, H, W)):          obs[r][t] = that frame, copied bit for bit;
+ *   sheet (NULL or uint8 (T+1, R*H, 3*W, 3)):      sheet 0, every block:  [zeros | start_u8 | goal_u8[0]] (never masked);
+ *                                                  sheet t+1, block r:    [zeros | u8(frame) as (H, W, 3) | goal_u8[g]],
+ *                                                  g = min(t, G-1), the goal pixel 0 where goal_mask[g] != 0.
+ * start_u8 (H, W, 3), goal_u8 (G, H, W, 3), goal_mask NULL or (G, H, W) uint8.  u8(v) is rac_predict_frames' rule: the
+ * fp32 product 255.0f * v (no fused multiply-add) clamped to [0, 255] and truncated toward zero, NaN -> 0, which is
+ * `np.uint8(255 * obs)` for v in [0, 1].
+ * W % 4 == 0; frames and obs 16-byte aligned, both strides multiples of 4; the uint8 buffers 4-byte aligned.  Every
+ * output byte and float has exactly one writer (no atomics).  R, T, G, H < 1, W % 4 != 0, NULL frames / rows, neither
+ * output, or a sheet without start_u8 / goal_u8: a non-zero status, rac_last_error() set, nothing launched. */
+int rac_cem_rollout_sheet(const float* frames, int64_t step_stride, int64_t cand_stride, const int32_t* rows, int32_t R,
+                          int32_t T, const uint8_t* start_u8, const uint8_t* goal_u8, int32_t G, const uint8_t* goal_mask,
+                          float* obs, uint8_t* sheet, int32_t H, int32_t W, void* stream);
+
 /* Robot-aware CEM inputs for ALL candidates on the device (replaces the per-candidate CPU loop of
  * `robot_model.predict_batch(start_data, thick=True)`, src/cem/trajectory_sampler.py:86-109 over
  * src/dataset/wx250s/wx250s_model.py:121-163 / locobot_model.py:100-140):

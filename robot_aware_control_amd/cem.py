@@ -15,6 +15,53 @@ from .state import DemoGoalState, State
 from .trajectory_sampler import TrajectorySampler
 
 
+def sheet_labels(n_blocks, T, H, has_opt, actions=None, first_step=0):
+    """The texts of the --debug_cem sheets as (sheet, x, y, text), (x, y) = the text's lower-left corner in the sheet
+    (cv2.putText's `org`; reference src/cem/cem.py:144-172, push/cem.py:202-233).  Sheet 0: "Start" in every row block.
+    Sheet t+1, block k (block k starts at row k*H): "Opt" (block 0 when `has_opt`) or "Rank j" at (0, 8); with `actions`
+    (n_blocks, T, >= 2) "X:..cm" / "Y:..cm" at (0, 16) / (0, 24); the step `t + first_step` at (64, 8), "GOAL" at (128, 8)."""
+    labels = [(0, 0, k * H + 8, "Start") for k in range(n_blocks)]
+    for t in range(T):
+        for k in range(n_blocks):
+            y = k * H
+            name = "Opt" if (has_opt and k == 0) else f"Rank {k - 1 if has_opt else k}"
+            labels.append((t + 1, 0, y + 8, name))
+            if actions is not None:
+                ac = actions[k][t]
+                labels.append((t + 1, 0, y + 16, f"X:{ac[0] * 100:.1f}cm"))
+                labels.append((t + 1, 0, y + 24, f"Y:{ac[1] * 100:.1f}cm"))
+            labels.append((t + 1, 64, y + 8, f"{t + first_step}"))
+            labels.append((t + 1, 128, y + 8, "GOAL"))
+    return labels
+
+
+def draw_labels(sheet, labels):
+    """`sheet` (S, rows, cols, 3) uint8 -> a list of S PIL images with the white texts of `labels` drawn in Pillow's
+    default font, the lower-left corner of each text's ink at its (x, y): the ink ends on the row above y and starts in
+    column x, whichever kind of font the Pillow at hand ships.  The glyphs are not cv2.putText's."""
+    from PIL import Image, ImageDraw, ImageFont
+    font = ImageFont.load_default()
+    imgs = [Image.fromarray(np.ascontiguousarray(f)) for f in sheet]
+    inks = {}
+    for s, x, y, text in labels:
+        ink = inks.get(text)
+        if ink is None:
+            left, top, right, bottom = font.getbbox(text)
+            ox, oy = 4 - min(left, 0), 4 - min(top, 0)
+            cell = Image.new("L", (int(right) + ox + 4, int(bottom) + oy + 4), 0)
+            ImageDraw.Draw(cell).text((ox, oy), text, font=font, fill=255)
+            box = cell.getbbox()
+            ink = inks[text] = cell.crop(box) if box else False
+        if ink:
+            imgs[s].paste((255, 255, 255), (x, y - ink.size[1]), ink)
+    return imgs
+
+
+def write_gif(path, imgs):
+    """Two frames per second, looping (imageio.mimwrite(path, gif, fps=2) in the reference)."""
+    imgs[0].save(path, save_all=True, append_images=imgs[1:], duration=500, loop=0)
+
+
 class CEMPolicy(object):
     """Given the current state and goal images, use CEM to find the best actions."""
 
@@ -38,6 +85,7 @@ class CEMPolicy(object):
         self.null_candidate = True  # cem.py:82-83; the sim variants do not force a do-nothing candidate
         self.gripper_clamp = None  # pick variant: (-0.01, 0) on the last action dim (pick/cem.py:88)
         self.plot_rollouts = cfg.debug_cem
+        self.last_sheet = self.last_gif = None  # debug_cem: the last call's unlabelled sheets and the GIF's path
         if self.plot_rollouts:
             self.debug_cem_dir = cfg.log_dir
             os.makedirs(self.debug_cem_dir, exist_ok=True)
@@ -95,8 +143,42 @@ class CEMPolicy(object):
         return torch.zeros(T - 1, A), torch.ones(T - 1, A) * self.init_std
 
     def _get_rollouts(self, act_seq, start: State, goal: DemoGoalState, opt_traj=None, plot=False):
-        return self.traj_sampler.generate_model_rollouts(act_seq, start, goal, ret_obs=self.plot_rollouts,
-                                                         opt_traj=opt_traj, suppress_print=True)
+        rollouts = self.traj_sampler.generate_model_rollouts(act_seq, start, goal, ret_obs=self.plot_rollouts,
+                                                             opt_traj=opt_traj, suppress_print=True)
+        if plot:  # the top-K model rollouts of the last CEM iteration (cem.py:128-178)
+            self._plot_model_rollouts(rollouts, act_seq, start, goal, opt_traj)
+        return rollouts
+
+    # what the real-robot sheet shows (cem.py:128-178); SimCEMPolicy overrides these four
+    def _plot_elites(self, topk_idx):
+        return topk_idx
+
+    def _plot_mask_goal(self, goal):
+        return False
+
+    def _plot_labels(self, n_blocks, T, H, act_seq, elites, opt_traj):
+        actions = np.asarray(act_seq[torch.as_tensor(np.asarray(elites), dtype=torch.long)][:, :, :2], dtype=np.float32)
+        if opt_traj is not None:
+            actions = np.concatenate([np.asarray(opt_traj, dtype=np.float32)[None, :, :2], actions])
+        return sheet_labels(n_blocks, T, H, opt_traj is not None, actions=actions)
+
+    def _plot_folder(self):
+        return self.debug_cem_dir
+
+    def _plot_model_rollouts(self, rollouts, act_seq, start, goal, opt_traj=None):
+        """`<folder>/step_<step>_top_k.gif`: one sheet per step, a row block [info | predicted frame | goal] per shown
+        candidate, composed on the device from the frames the rollouts left there (TrajectorySampler.rollout_sheet);
+        only the texts are drawn on the host.  Keeps the unlabelled sheet in `last_sheet`, the path in `last_gif`."""
+        elites = [int(i) for i in self._plot_elites(np.asarray(rollouts["topk_idx"]))]
+        rows = ([len(act_seq)] if opt_traj is not None else []) + elites  # the opt row is the sampler's candidate N
+        sheet = self.traj_sampler.rollout_sheet(rows, start, goal, mask_goal=self._plot_mask_goal(goal))
+        H = sheet.shape[1] // len(rows)
+        labels = self._plot_labels(len(rows), sheet.shape[0] - 1, H, act_seq, elites, opt_traj)
+        folder = self._plot_folder()
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, f"step_{self.step}_top_k.gif")
+        write_gif(path, draw_labels(sheet, labels))
+        self.last_sheet, self.last_gif = sheet, path
 
 
 class SimCEMPolicy(CEMPolicy):
@@ -136,3 +218,17 @@ class SimCEMPolicy(CEMPolicy):
             mean[:, -1] = -0.005
             std[:, -1] = 0.005
         return mean, std
+
+    # _plot_model_rollouts of push/cem.py:183-239: at most 5 elites, goals blacked by their masks for the dontcare
+    # reward, steps counted from 1, no action texts, one folder per episode
+    def _plot_elites(self, topk_idx):
+        return topk_idx[:min(len(topk_idx), 5)]
+
+    def _plot_mask_goal(self, goal):
+        return goal.masks is not None and self.cfg.reward_type == "dontcare"
+
+    def _plot_labels(self, n_blocks, T, H, act_seq, elites, opt_traj):
+        return sheet_labels(n_blocks, T, H, opt_traj is not None, first_step=1)
+
+    def _plot_folder(self):
+        return os.path.join(self.debug_cem_dir, f"ep_{self.ep_num}")

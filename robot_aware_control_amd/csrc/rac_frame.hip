@@ -358,6 +358,72 @@ __global__ void predict_frames_kernel(const f32x4* x4, const float* prev, const 
   }
 }
 
+// ---- planner debug sheet ------------------------------------------------------
+// The --debug_cem top-K sheet (cem.py:128-178, push/cem.py:183-239) from the candidates' frames as the step tail left
+// them on the device: row block r of sheet t + 1 is [zeros | u8(frame of candidate rows[r] at step t) | goal], sheet 0 is
+// [zeros | start | goal 0] in every block; `obs` takes the same frames as plain fp32 copies (rollouts["obs"]).  A thread
+// owns 4 consecutive pixels of one image row of one block (W % 4 == 0): three float4 loads from the store, three
+// float4 stores to obs, and 12 contiguous bytes to each of the three panels, so every byte and float has one writer.
+__global__ void cem_rollout_sheet_kernel(const float* frames, long step_stride, long cand_stride, const int* rows, int R,
+                                         int T, const unsigned char* start_u8, const unsigned char* goal_u8, int G,
+                                         const unsigned char* goal_mask, float* obs, unsigned char* sheet, int H, int W) {
+  const int QW = W >> 2;  // pixel quads per image row
+  const long HW = (long)H * W;
+  const long per_block = (long)H * QW, per_sheet = (long)R * per_block;
+  const int s0 = sheet ? 0 : 1;  // obs alone: sheet 0 (start | goal) has nothing to do
+  const long nq = (long)(T + 1 - s0) * per_sheet;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nq; i += (long)gridDim.x * blockDim.x) {
+    const long sb = i / per_sheet;
+    const long in_sheet = i - sb * per_sheet;
+    const int s = (int)sb + s0;
+    const int r = (int)(in_sheet / per_block);
+    const int in_block = (int)(in_sheet - r * per_block);
+    const int y = in_block / QW;
+    const long pix = (long)y * W + ((in_block - y * QW) << 2);
+    // panel 0 of this thread's pixels; panels 1 and 2 follow at 3 W and 6 W bytes
+    // (a sheet row is 9 W bytes: ((s R + r) H + y) 9 W + 3 x = 3 ((s R + r) 3 H W + 2 y W + pix))
+    unsigned* o = sheet ? reinterpret_cast<unsigned*>(sheet + (((long)s * R + r) * HW * 3 + (long)y * W * 2 + pix) * 3)
+                        : nullptr;
+    const int pw = (3 * W) >> 2;  // a panel row in words
+    int g = 0;
+    if (s == 0) {
+      const unsigned* st = reinterpret_cast<const unsigned*>(start_u8 + pix * 3);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) o[pw + k] = st[k];
+    } else {
+      const int t = s - 1;
+      g = t < G ? t : G - 1;
+      const float* src = frames + t * step_stride + rows[r] * cand_stride + pix;
+      f32x4 v[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = *reinterpret_cast<const f32x4*>(src + c * HW);
+      if (obs) {
+        float* d = obs + ((long)r * T + t) * 3 * HW + pix;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4*>(d + c * HW) = v[c];
+      }
+      if (o) store_rgb4(reinterpret_cast<unsigned char*>(o + pw), v, f32x4{0.f, 0.f, 0.f, 0.f});
+    }
+    if (!o) continue;
+    const unsigned* gl = reinterpret_cast<const unsigned*>(goal_u8 + ((long)g * HW + pix) * 3);
+    unsigned gw[3] = {gl[0], gl[1], gl[2]};
+    if (s > 0 && goal_mask) {  // black the goal's robot pixels: pixel j is bits [24 j, 24 j + 24) of the 12 bytes
+      const unsigned m = *reinterpret_cast<const unsigned*>(goal_mask + (long)g * HW + pix);
+      unsigned keep[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) keep[j] = ((m >> (8 * j)) & 0xffu) ? 0u : 0xffffffu;
+      gw[0] &= keep[0] | (keep[1] << 24);
+      gw[1] &= (keep[1] >> 8) | (keep[2] << 16);
+      gw[2] &= (keep[2] >> 16) | (keep[3] << 8);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      o[k] = 0u;
+      o[2 * pw + k] = gw[k];
+    }
+  }
+}
+
 // ---- reconstruction losses --------------------------------------------------
 // per_sample[b][0..7]: 0 main sum, 1 #world values (3 per unmasked pixel), 2 sum robot d^2, 3 #robot values,
 //                      4 sum world d^2
@@ -772,6 +838,25 @@ int rac_predict_frames(const float* x4, const float* prev, const float* target, 
   hipLaunchKernelGGL(predict_frames_kernel, dim3(grid_for((long)n * (HW / 4))), dim3(256), 0, ST(stream),
                      (const f32x4*)x4, prev, target, true_mask, pred, gen_u8, true_u8, (long)image_stride, n, nt, HW);
   return check_launch("rac_predict_frames");
+}
+
+int rac_cem_rollout_sheet(const float* frames, int64_t step_stride, int64_t cand_stride, const int32_t* rows, int32_t R,
+                          int32_t T, const uint8_t* start_u8, const uint8_t* goal_u8, int32_t G, const uint8_t* goal_mask,
+                          float* obs, uint8_t* sheet, int32_t H, int32_t W, void* stream) {
+  RAC_REQUIRE(frames && rows && R >= 1 && T >= 1 && G >= 1 && H >= 1 && W >= 1 && (obs || sheet),
+              "rac_cem_rollout_sheet: bad args (frames, rows, R, T, G, H >= 1 and at least one of obs / sheet)");
+  RAC_REQUIRE(W % 4 == 0, "rac_cem_rollout_sheet: W %% 4 == 0 (a thread owns 4 pixels of a row)");
+  RAC_REQUIRE(!sheet || (start_u8 && goal_u8), "rac_cem_rollout_sheet: a sheet needs start_u8 and goal_u8");
+  auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
+  RAC_REQUIRE(aligned16(frames) && step_stride % 4 == 0 && cand_stride % 4 == 0 && step_stride >= 0 && cand_stride >= 0 &&
+                  (!obs || aligned16(obs)) &&
+                  (!sheet || (aligned4(sheet) && aligned4(start_u8) && aligned4(goal_u8) && aligned4(goal_mask))),
+              "rac_cem_rollout_sheet: 16-byte aligned float buffers, strides multiples of 4, 4-byte aligned uint8 buffers");
+  const long quads = (long)(T + 1) * R * H * (W / 4);
+  RAC_REQUIRE((long)H * W < (1L << 29) && quads < (1L << 40), "rac_cem_rollout_sheet: too many pixels");
+  hipLaunchKernelGGL(cem_rollout_sheet_kernel, dim3(grid_for(quads)), dim3(256), 0, ST(stream), frames, (long)step_stride,
+                     (long)cand_stride, rows, R, T, start_u8, goal_u8, G, goal_mask, obs, sheet, H, W);
+  return check_launch("rac_cem_rollout_sheet");
 }
 
 int rac_recon_loss_fwd(int32_t kind, const float* pred, const float* target, const float* mask, float robot_weight,

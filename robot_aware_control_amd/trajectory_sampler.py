@@ -4,7 +4,9 @@
 Per (batch, step) the reference runs model.forward, two elementwise passes, a cost reduction and a
 device->host copy (70 syncs per CEM iteration at N=1000).  Here the step tail -- compositing,
 zero_robot_region, the image cost and its fp64 accumulation -- is one kernel and the per-candidate
-sums stay on the device until the end: one D2H per call.
+sums stay on the device until the end: one D2H per call.  With `ret_obs` (the planner's --debug_cem) the step tail
+writes every candidate's frame into a device store; the elites' frames leave it in one more D2H once the ranking is known,
+and `rollout_sheet` composes the debug GIF's sheets from it (rac_cem_rollout_sheet).
 
 Multi-GPU: candidates are independent, so with torch.distributed initialised each rank rolls out
 its contiguous slice and ONE all-gather (RCCL over xGMI) of the per-candidate fp64 costs precedes
@@ -60,6 +62,10 @@ class TrajectorySampler(object):
         self.robot_model = robot_model
         self._refining = False  # inside the exact re-roll of the elites (no sharding, no nested refinement)
         self._robot_ctor = (cam_ext, franka_ik, wx250s_bot, push_height, default_pitch, default_roll)
+        self._obs_store = None        # (T, n, 3, H, W) fp32 on the device: every candidate's frames of a `ret_obs` call
+        self._obs_last = None         # (store, opt row or None) of the last `ret_obs` call, for rollout_sheet
+        self.last_obs_d2h_bytes = 0   # what the last `ret_obs` call copied to the host for rollouts["obs"/"optimal_obs"]
+        self.last_obs_d2h_copies = 0
         if os.environ.get("RAC_GC_FREEZE", "0") == "1":  # opt-in, see PredictionTrainer.__init__
             import gc
             gc.collect()
@@ -149,6 +155,69 @@ class TrajectorySampler(object):
         self.last_refined = top
         return sum_cost
 
+    def _frame_store(self, T, n, H, W, dev):
+        """The `ret_obs` frame store: one fp32 (T, n, 3, H, W) device buffer, kept on the sampler and reused while the
+        shape stays (the planner asks with the same shape in every iteration but the last, which adds the opt row).
+        T n 3 H W 4 bytes, uncapped: 0.52 GB at 1000 candidates x 14 steps of 48 x 64."""
+        shape = (T, n, 3, H, W)
+        st = self._obs_store
+        if st is None or tuple(st.shape) != shape or st.device != dev:
+            self._obs_store = self._obs_last = st = None  # free the old one before the new one is allocated
+            st = self._obs_store = torch.empty(shape, device=dev, dtype=torch.float32)
+        return st
+
+    def release_obs_store(self):
+        """Free the `ret_obs` frame store (the next `ret_obs` call allocates it again)."""
+        self._obs_store = self._obs_last = None
+
+    def _sheet_launch(self, rows, start_u8=None, goal_u8=None, goal_mask=None, want_obs=False, want_sheet=False):
+        """One rac_cem_rollout_sheet launch over the last `ret_obs` call's store: (obs, sheet) device tensors."""
+        if self._obs_last is None:
+            raise _lib.RacError("no frame store: call generate_model_rollouts(ret_obs=True) first")
+        store = self._obs_last[0]
+        T, n, _, H, W = store.shape
+        rows = [int(r) for r in rows]
+        if not rows or min(rows) < 0 or max(rows) >= n:
+            raise _lib.RacError(f"rollout rows {rows} outside the {n} candidates of the frame store")
+        dev = store.device
+        rows_dev = torch.tensor(rows, dtype=torch.int32).to(dev)
+        R = len(rows)
+        obs = torch.empty((R, T, 3, H, W), device=dev, dtype=torch.float32) if want_obs else None
+        sheet = torch.empty((T + 1, R * H, 3 * W, 3), device=dev, dtype=torch.uint8) if want_sheet else None
+        G = 1 if goal_u8 is None else goal_u8.shape[0]
+        _lib.call("rac_cem_rollout_sheet", store.data_ptr(), store.stride(0), store.stride(1), rows_dev.data_ptr(), R, T,
+                  _lib.ptr(start_u8), _lib.ptr(goal_u8), G, _lib.ptr(goal_mask), _lib.ptr(obs), _lib.ptr(sheet), H, W,
+                  _lib.stream_ptr())
+        return obs, sheet
+
+    @torch.no_grad()
+    def rollout_sheet(self, rows, start: State, goal: DemoGoalState, mask_goal=False) -> np.ndarray:
+        """The unlabelled --debug_cem sheet (reference src/cem/cem.py:140-175), uint8 (T+1, R*H, 3W, 3): row block r of
+        sheet t+1 is [zeros | frame of candidate rows[r] at step t | goal t], sheet 0 [zeros | start | goal 0].  `rows`
+        index the candidates of the last `ret_obs` call (its opt_traj row is the last one).  `mask_goal`: goals blacked
+        by `goal.masks` from sheet 1 on (push/cem.py:210-212).  One launch, one device-to-host copy."""
+        if self._obs_last is None:
+            raise _lib.RacError("no frame store: call generate_model_rollouts(ret_obs=True) first")
+        store = self._obs_last[0]
+        H, W = store.shape[3], store.shape[4]
+        dev = store.device
+
+        def u8(img):
+            a = np.ascontiguousarray(np.asarray(img), dtype=np.uint8)
+            if a.shape != (H, W, 3):
+                raise _lib.RacError(f"rollout_sheet: image of shape {a.shape}, the frames are ({H}, {W}, 3)")
+            return a
+        start_u8 = torch.from_numpy(u8(start.img)).to(dev)
+        goal_u8 = torch.from_numpy(np.stack([u8(g) for g in goal.imgs])).to(dev)
+        goal_mask = None
+        if mask_goal:
+            if goal.masks is None or len(goal.masks) != len(goal.imgs):
+                raise _lib.RacError("rollout_sheet: mask_goal needs one goal mask per goal image")
+            m = np.stack([np.asarray(g).reshape(H, W) != 0 for g in goal.masks]).astype(np.uint8)
+            goal_mask = torch.from_numpy(m).to(dev)
+        _, sheet = self._sheet_launch(rows, start_u8, goal_u8, goal_mask, want_sheet=True)
+        return sheet.cpu().numpy()
+
     @torch.no_grad()
     def generate_model_rollouts(self, action_sequences, start: State, goal: DemoGoalState, opt_traj=None,
                                 ret_obs=False, ret_step_cost=False, suppress_print=True):
@@ -195,7 +264,12 @@ class TrajectorySampler(object):
         per = cfg.candidates_batch_size
         nb = max(n_local // per, 1)
         sum_cost_dev = torch.zeros(max(n_local, 1), device=dev, dtype=torch.float64)
-        all_obs = torch.zeros((N, T, 3, H, W)) if ret_obs else None
+        # ret_obs: every step's composite frame is written by the step tail straight into the device store (ret_obs
+        # disables sharding: n_local == N); the elites' frames are picked out of it once the ranking is known
+        store = None
+        if ret_obs:
+            self._obs_last = None  # the store is being overwritten: no sheet of it until this call has finished
+            store = self._frame_store(T, n_local, H, W, dev)
         step_cost = np.zeros((N, T)) if ret_step_cost else None
         start_img = (torch.from_numpy(start.img.copy()).permute(2, 0, 1).float() / 255).to(dev)
         actions_dev = action_sequences.to(dev, torch.float32)
@@ -227,7 +301,7 @@ class TrajectorySampler(object):
                                         shared_frame=shared)[0]
                 gi = t if t < len(goal_imgs) else -1
                 add = (not cfg.sparse_cost) or t == T - 1
-                nxt = torch.empty_like(curr)
+                nxt = store[t, ls:le] if ret_obs else torch.empty_like(curr)  # (a contiguous slice of the store)
                 before = sum_cost_dev[ls:le].clone() if ret_step_cost else None
                 # locals: the (possibly copied) operands must outlive the raw-pointer launch
                 next_mask = masks[t + 1, ls:le].contiguous() if (dontcare_in or dontcare_cost) else None
@@ -238,8 +312,6 @@ class TrajectorySampler(object):
                     goal_img.data_ptr(), _lib.ptr(next_mask) if dontcare_cost else None, _lib.ptr(goal_mask),
                     kind, w_world, 1 if (add and w_world != 0) else 0, nxt.data_ptr(),
                     sum_cost_dev[ls:le].data_ptr(), n, H * W, _lib.stream_ptr())
-                if ret_obs:
-                    all_obs[s:e, t] = nxt.cpu()
                 if ret_step_cost:
                     step_cost[s:e, t] = (sum_cost_dev[ls:le] - before).cpu().numpy()
                 curr = nxt
@@ -257,14 +329,27 @@ class TrajectorySampler(object):
         if opt_traj is not None:
             rollouts["optimal_sum_cost"] = sum_cost[-1]
             if ret_obs:
-                rollouts["optimal_obs"] = all_obs[-1].numpy()
+                rollouts["optimal_obs"] = None  # (keeps its place among the keys; filled with the elites' frames below)
             sum_cost = sum_cost[:-1]
         sum_cost = self._refine_elites(sum_cost, action_sequences, start, goal)
         rollouts["sum_cost"] = sum_cost
         if ret_obs:
             topk_idx = np.argsort(sum_cost)[-cfg.topk:]
             rollouts["topk_idx"] = topk_idx
-            rollouts["obs"] = all_obs[topk_idx].numpy()
+            # the elites' (and the opt row's) frames out of the store: one launch, one device-to-host copy
+            opt_row = N - 1 if opt_traj is not None else None
+            self._obs_last = (store, opt_row)
+            rows = list(topk_idx) + ([opt_row] if opt_row is not None else [])
+            self.last_obs_d2h_bytes = self.last_obs_d2h_copies = 0
+            if rows:
+                picked = self._sheet_launch(rows, want_obs=True)[0].cpu()
+                self.last_obs_d2h_bytes, self.last_obs_d2h_copies = picked.numel() * picked.element_size(), 1
+                picked = picked.numpy()
+            else:
+                picked = np.zeros((0, T, 3, H, W), np.float32)
+            rollouts["obs"] = picked[:len(topk_idx)]
+            if opt_row is not None:
+                rollouts["optimal_obs"] = picked[-1]
         if ret_step_cost:
             rollouts["step_cost"] = step_cost[:len(sum_cost)]
         return rollouts
