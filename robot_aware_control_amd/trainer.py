@@ -15,6 +15,7 @@ import os
 from collections import defaultdict
 from glob import glob
 from math import floor
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -232,6 +233,49 @@ class PredictionTrainer(object):
             self._grad_seeds[key] = t
         return self._grad_seeds[key]
 
+    # ---------------------------------------------------------------- windows
+    def _robot_windows(self):
+        """Do this run's windows take their states and masks from `self.robot_model` (finetune_* experiments of a model
+        that takes masks or robot states: trainer.py:294-319, 520-547, 1180-1202)?  Refuses such a run without one."""
+        cf = self._config
+        if not ("finetune" in cf.experiment and (cf.model_use_mask or cf.model_use_robot_state)):
+            return False
+        if getattr(self, "robot_model", None) is None:
+            raise NotImplementedError(
+                "finetune_* windows take their robot states and masks from an analytical / learned robot model: set "
+                "`trainer.robot_model` to an object with predict_batch(batch) -> (states, masks[, heatmaps]) -- the "
+                "reference's LocobotAnalyticalModel, robot_atlas.AtlasRobotModel or robot_model.LearnedRobotModel")
+        return True
+
+    def _window_batch(self, data, s, e, predicted_masks_key):
+        """Frames [s, e) of a time-first video as the batch of one step.  Under `_robot_windows` the robot model's states,
+        masks and (with `model_use_heatmap`) heatmaps replace the window's `states`, `predicted_masks_key` and `heatmaps`:
+        training rolls out and scores on the predicted masks ("masks"); an evaluation rolls out on them ("pred_masks")
+        and scores with the true ones, which stay in `masks`.  `qpos` and `folder` are the learned robot model's inputs
+        and are carried whenever the video has them (views: no step reads them)."""
+        cf = self._config
+        batch = {"images": data["images"][s:e], "states": data["states"][s:e], "actions": data["actions"][s:e - 1],
+                 "masks": data["masks"][s:e], "robot": data["robot"]}
+        batch[predicted_masks_key] = batch["masks"]
+        if "qpos" in data:
+            batch["qpos"] = data["qpos"][s:e]
+        if "folder" in data:  # the learned robot model renders each sample from its own viewpoint
+            batch["folder"] = data["folder"]
+        use_heatmap = getattr(cf, "model_use_heatmap", False)
+        if use_heatmap:
+            batch["heatmaps"] = data["heatmaps"][s:e]
+        if self._robot_windows():
+            if getattr(cf, "preprocess_action", "raw") != "raw":
+                batch["raw_actions"], batch["raw_states"] = data["raw_actions"][s:e - 1], data["raw_states"][s:e]
+                batch["raw_low"], batch["raw_high"] = data["raw_low"], data["raw_high"]
+            batch["low"], batch["high"] = data["low"], data["high"]
+            out = self.robot_model.predict_batch(batch)
+            if use_heatmap:
+                batch["states"], batch[predicted_masks_key], batch["heatmaps"] = out
+            else:
+                batch["states"], batch[predicted_masks_key] = out
+        return batch
+
     # ------------------------------------------------------------- train step
     def _train_video(self, data):
         """Slice a video into n_past+n_future windows and train on each (trainer.py:259-324)."""
@@ -247,34 +291,49 @@ class PredictionTrainer(object):
                 e = s + window
             else:
                 s, e = i * window, (i + 1) * window
-            batch = {"images": x[s:e], "states": data["states"][s:e], "actions": data["actions"][s:e - 1],
-                     "masks": data["masks"][s:e], "robot": data["robot"], "folder": data.get("folder")}
-            if "qpos" in data:
-                batch["qpos"] = data["qpos"][s:e]
-            if getattr(cf, "model_use_heatmap", False):
-                batch["heatmaps"] = data["heatmaps"][s:e]
+            batch = self._window_batch(data, s, e, "masks")
             if cf.load_movement_info:
                 batch["high_movement"] = data["high_movement"]
-            if "finetune" in cf.experiment and (cf.model_use_mask or cf.model_use_robot_state):
-                # finetune_*: states and masks of the window come from a robot model (trainer.py:294-319)
-                if getattr(cf, "preprocess_action", "raw") != "raw":
-                    batch["raw_actions"], batch["raw_states"] = data["raw_actions"][s:e - 1], data["raw_states"][s:e]
-                    batch["raw_low"], batch["raw_high"] = data["raw_low"], data["raw_high"]
-                batch["low"], batch["high"] = data["low"], data["high"]
-                if getattr(self, "robot_model", None) is None:
-                    raise NotImplementedError(
-                        "finetune_* windows take their robot states and masks from an analytical / learned robot model "
-                        "(trainer.py:294-319): set `trainer.robot_model` to an object with predict_batch(batch) -> "
-                        "(states, masks) -- the reference's LocobotAnalyticalModel, or robot_atlas.AtlasRobotModel")
-                out = self.robot_model.predict_batch(batch)
-                if getattr(cf, "model_use_heatmap", False):
-                    batch["states"], batch["masks"], batch["heatmaps"] = out
-                else:
-                    batch["states"], batch["masks"] = out
             losses = self._train_step(batch)
             for k, v in losses.items():
                 all_losses[k] += v / floor(T / window)
         return all_losses
+
+    def _model_step(self, i, x_j, masks, states, ac, heatmaps, skip, *, posterior, force_use_prior=False, dontcare):
+        """One model step of a rollout: frame i's decoder output from the frame `x_j` fed as frame i - 1 and the window's
+        (T, B, ...) `masks`, `states`, `ac` and `heatmaps` (None: no heatmap input).  Returns (x4, the skip maps for the
+        next step, (mu, logvar, mu_p, logvar_p)) -- `--model det` has no latents: None.  The caller picks `x_j`,
+        composites `x4` over it and scores the frame."""
+        cf = self._config
+        m_j, r_j, a_j = masks[i - 1], states[i - 1], ac[i - 1]
+        if cf.last_frame_skip:
+            skip = None
+        m_in = torch.cat([m_j, masks[i]], 1) if cf.model_use_future_mask else m_j
+        zero_mask = m_j if dontcare else None
+        if cf.model == "det":  # trainer.py:383-384, 628-629: no prior / posterior, no future robot state, no heatmap
+            x4, curr_skip = self.model.forward_maps(x_j, m_in, r_j, a_j, skip, zero_mask=zero_mask)
+            latents = None
+        else:
+            r_in = (r_j, states[i]) if cf.model_use_future_robot_state else r_j
+            hm_in = None
+            if heatmaps is not None:
+                hm_in = torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap else heatmaps[i - 1]
+            x4, curr_skip, *latents = self.model.forward_maps(
+                x_j, m_in, r_in, hm_in, a_j, posterior, states[i] if posterior else None, skip,
+                force_use_prior=force_use_prior, zero_mask=zero_mask)
+        return x4, (curr_skip if i <= cf.n_past else skip), latents  # the encoder's skip maps of the context frames only
+
+    def _per_robot_losses(self, x_pred, x_i, m_i, robot_name, all_robots):
+        """[(robot, its samples' (3,) [loss, robot_mse, world_mse])] of a batch that mixes robots: the per-robot logging
+        metrics (trainer.py:442-452); nothing for a batch of one robot."""
+        if len(all_robots) < 2:
+            return []
+        subs = []
+        for r in all_robots:
+            idx = torch.from_numpy(np.nonzero(robot_name == r)[0]).to(self._device)
+            subs.append((r, ops.ReconLoss.apply(x_pred[idx].contiguous(), x_i[idx].contiguous(), m_i[idx].contiguous(),
+                                                None, 0, 0.0)))
+        return subs
 
     def _train_step(self, data, use_truth=None):
         """Forward and backward pass + optimiser step (trainer.py:326-465).  Returns the loss dict.
@@ -310,21 +369,17 @@ class PredictionTrainer(object):
         roots, seeds, log = [], [], []  # autograd roots, their incoming grads, (name, tensor, index) for the readback
         n_steps = cf.n_past + cf.n_future - 1
 
-        def add_losses(x_pred, i, mu, logvar, mu_p, logvar_p, kl_here=True):
+        def add_losses(x_pred, i, latents, kl_here=True):
             x_i, m_i = x[i], mask[i]
             rec = self._recon_loss(x_pred, x_i.contiguous(), m_i.contiguous(), batch_weight)
             roots.append(rec)
             seeds.append(self._seed(1.0, 3, first_only=True))
             log.extend([("recon_loss", rec, 0), ("robot_loss", rec, 1), ("world_loss", rec, 2)])
-            if len(all_robots) > 1:  # per-robot logging metrics (trainer.py:442-452)
-                with torch.no_grad():
-                    for r in all_robots:
-                        idx = torch.from_numpy(np.nonzero(robot_name == r)[0]).to(dev)
-                        sub = ops.ReconLoss.apply(x_pred.detach()[idx].contiguous(), x_i[idx].contiguous(),
-                                                  m_i[idx].contiguous(), None, 0, 0.0)
-                        log.extend([(f"{r}_robot_loss", sub, 1), (f"{r}_world_loss", sub, 2)])
+            with torch.no_grad():
+                for r, sub in self._per_robot_losses(x_pred.detach(), x_i, m_i, robot_name, all_robots):
+                    log.extend([(f"{r}_robot_loss", sub, 1), (f"{r}_world_loss", sub, 2)])
             if kl_here:
-                add_kl(mu, logvar, mu_p, logvar_p)
+                add_kl(*latents)
 
         def add_kl(mu, logvar, mu_p, logvar_p):
             kl = ops.KLLoss.apply(mu, logvar, mu_p, logvar_p, bs)
@@ -364,7 +419,7 @@ class PredictionTrainer(object):
                 log.extend([("recon_loss", rec, 0, T), ("robot_loss", rec, 1, T), ("world_loss", rec, 2, T)])
             else:
                 for t in range(T):
-                    add_losses(x_preds[t], t + 1, mus[t], logvars[t], mu_ps[t], logvar_ps[t], kl_here=batched is None)
+                    add_losses(x_preds[t], t + 1, (mus[t], logvars[t], mu_ps[t], logvar_ps[t]), kl_here=batched is None)
             if batched is not None:
                 # sum_t KL_t: every term is a sum over its elements / bs (losses.py:97-106), so the window's KL is ONE
                 # launch over all T*B samples' elements (and one backward launch writing the batched gradients)
@@ -374,26 +429,10 @@ class PredictionTrainer(object):
             skip = None
             for i in range(1, n_steps + 1):
                 x_j = x[i - 1] if truths[i - 1] else x_pred  # scheduled sampling: gradients flow through the fed-back frame
-                m_j, r_j, a_j = mask[i - 1], states[i - 1], ac[i - 1]
-                m_i, r_i = mask[i], states[i]
-                if cf.last_frame_skip:
-                    skip = None
-                m_in = torch.cat([m_j, m_i], 1) if cf.model_use_future_mask else m_j
-                r_in = (r_j, r_i) if cf.model_use_future_robot_state else r_j
-                hm_in = None
-                if heatmaps is not None:
-                    hm_in = (torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap
-                             else heatmaps[i - 1])
-                mu = logvar = mu_p = logvar_p = None
-                if det:
-                    x4, curr_skip = self.model.forward_maps(x_j, m_in, r_j, a_j, skip, zero_mask=m_j if dontcare else None)
-                else:
-                    x4, curr_skip, mu, logvar, mu_p, logvar_p = self.model.forward_maps(
-                        x_j, m_in, r_in, hm_in, a_j, True, r_i, skip, zero_mask=m_j if dontcare else None)
+                x4, skip, latents = self._model_step(i, x_j, mask, states, ac, heatmaps, skip, posterior=True,
+                                                     dontcare=dontcare)
                 x_pred = ops.Composite.apply(x4, x_j.contiguous())  # un-blacked x_j (trainer.py:406-407)
-                if i <= cf.n_past:
-                    skip = curr_skip
-                add_losses(x_pred, i, mu, logvar, mu_p, logvar_p, kl_here=not det)
+                add_losses(x_pred, i, latents, kl_here=not det)
         # the step's loss scalars are final once the forward pass is enqueued: start their device->host copy now (into
         # pinned memory) and collect it after the optimiser step is enqueued, so that the host never waits for the
         # backward pass or Adam (the reference likewise reads its losses before loss.backward(), trainer.py:433-458)
@@ -473,37 +512,12 @@ class PredictionTrainer(object):
         self.last_best_eval_sample = 0
         batched = os.environ.get("RAC_PREDICT_BATCH_SAMPLES", "1") == "1"
         sampled = [defaultdict(float) for _ in range(num_samples)]
-        finetune = "finetune" in cf.experiment and (cf.model_use_mask or cf.model_use_robot_state)
-        if finetune and getattr(self, "robot_model", None) is None:
-            raise NotImplementedError(
-                "finetune_* evaluation rolls out on the robot model's states and masks (trainer.py:520-543): set "
-                "`trainer.robot_model` (the reference's LocobotAnalyticalModel, or robot_atlas.AtlasRobotModel)")
-        x = data["images"]
-        T = len(x)
+        self._robot_windows()  # (a finetune_* run without a robot model is refused before its first window)
+        T = len(data["images"])
         window = cf.n_eval
         total = defaultdict(float)
         for i in range(floor(T / window)):
-            s, e = i * window, (i + 1) * window
-            batch = {"images": x[s:e], "states": data["states"][s:e], "actions": data["actions"][s:e - 1],
-                     "masks": data["masks"][s:e], "pred_masks": data["masks"][s:e], "robot": data["robot"]}
-            if getattr(cf, "model_use_heatmap", False):
-                batch["heatmaps"] = data["heatmaps"][s:e]
-            if finetune:
-                # predicted states / masks drive the rollout, the true masks score the world error (trainer.py:520-547)
-                for k in ("qpos",):
-                    if k in data:
-                        batch[k] = data[k][s:e]
-                if "folder" in data:  # the learned robot model renders each sample from its own viewpoint
-                    batch["folder"] = data["folder"]
-                if getattr(cf, "preprocess_action", "raw") != "raw":
-                    batch["raw_actions"], batch["raw_states"] = data["raw_actions"][s:e - 1], data["raw_states"][s:e]
-                    batch["raw_low"], batch["raw_high"] = data["raw_low"], data["raw_high"]
-                batch["low"], batch["high"] = data["low"], data["high"]
-                out = self.robot_model.predict_batch(batch)
-                if getattr(cf, "model_use_heatmap", False):
-                    batch["states"], batch["pred_masks"], batch["heatmaps"] = out
-                else:
-                    batch["states"], batch["pred_masks"] = out
+            batch = self._window_batch(data, i * window, (i + 1) * window, "pred_masks")
             if num_samples == 1:
                 for k, v in self._eval_step(batch, autoregressive).items():
                     total[k] += v
@@ -531,6 +545,55 @@ class PredictionTrainer(object):
             order.sort(key=lambda n: sampled[n]["autoreg_psnr"], reverse=True)
         return order[0]
 
+    def _snippet(self, data, autoregressive, S=1):
+        """An n_eval snippet on the device, ready for a prior-driven rollout of S samples as ONE batch of S B videos:
+        the recurrent states are reset for S B videos and the rollout's inputs (`states`, `ac`, `masks`: the batch's
+        `pred_masks`, `heatmaps`) repeated per sample group, group s in rows [s B, (s+1) B); the frames `x` and the
+        scoring masks `true_masks` stay (B, ...), `frame_in(i)` is frame i for all groups."""
+        cf = self._config
+        dev, f32 = self._device, torch.float32
+        svg = cf.model == "svg"  # det (trainer.py:628-629) and copy (:606-607) have no prior: no KL term, no heatmap
+        if S > 1 and not svg:
+            raise ValueError("only --model svg draws samples")
+        sn = SimpleNamespace(svg=svg, prefix="autoreg" if autoregressive else "1step",
+                             dontcare="dontcare" in cf.reconstruction_loss or cf.black_robot_input)
+        sn.x = x = data["images"].to(dev, f32)
+        sn.states = data["states"].to(dev, f32)
+        sn.ac = data["actions"].to(dev, f32)
+        sn.true_masks = data["masks"].to(dev, f32)
+        sn.masks = data["pred_masks"].to(dev, f32)
+        sn.heatmaps = data["heatmaps"].to(dev, f32) if getattr(cf, "model_use_heatmap", False) and svg else None
+        sn.robot_name = np.array(data["robot"])
+        sn.all_robots = sorted(set(sn.robot_name))
+        sn.bs = min(cf.test_batch_size, x.shape[1])
+        self.model.init_hidden(S * sn.bs)
+        if S > 1:
+            rep = lambda t: t.repeat((1, S) + (1,) * (t.dim() - 2))
+            sn.states, sn.ac, sn.masks = rep(sn.states), rep(sn.ac), rep(sn.masks)
+            sn.heatmaps = rep(sn.heatmaps) if sn.heatmaps is not None else None
+        sn.frame_in = lambda i: x[i] if S == 1 else x[i].repeat(S, 1, 1, 1)
+        return sn
+
+    def _prior_rollout(self, sn, autoregressive, composite=None):
+        """Roll the snippet `sn` (`_snippet`) out on the prior (`force_use_prior`; the posterior runs for the KL term):
+        frame i is predicted from frame i - 1, or from the prediction of it when `autoregressive`.
+        `composite(i, x4, x_j, x_i, true_mask_i)` makes the frame from the decoder's output (None: `ops.Composite` over
+        the frame fed in).  `--model copy` has no model
+        step and nothing to composite: its frame is the one fed in, on the rollout's masks (`pred_masks`).
+        Yields (i, x_pred (S B, 3, H, W), latents or None, x[i], true_masks[i]) per step, for the caller to score."""
+        cf = self._config
+        x_pred = skip = None
+        for i in range(1, cf.n_eval):
+            x_j = x_pred if (autoregressive and i > 1) else sn.frame_in(i - 1)
+            x_i, tm = sn.x[i].contiguous(), sn.true_masks[i].contiguous()
+            if cf.model == "copy":
+                x_pred, latents = self.model(x_j, sn.masks[i - 1], x_i, sn.masks[i]), None
+            else:
+                x4, skip, latents = self._model_step(i, x_j, sn.masks, sn.states, sn.ac, sn.heatmaps, skip,
+                                                     posterior=True, force_use_prior=True, dontcare=sn.dontcare)
+                x_pred = composite(i, x4, x_j, x_i, tm) if composite else ops.Composite.apply(x4, x_j.contiguous())
+            yield i, x_pred, latents, x_i, tm
+
     @torch.no_grad()
     def _eval_step(self, data, autoregressive=False, num_samples=None):
         """Evaluate one n_eval snippet (trainer.py:566-734): prior-driven prediction (`force_use_prior`), optional
@@ -546,61 +609,21 @@ class PredictionTrainer(object):
             return self._eval_step_sampled(data, autoregressive, int(num_samples))
         from .metrics import masked_psnr_ssim
         cf = self._config
-        dev, f32 = self._device, torch.float32
-        x = data["images"].to(dev, f32)
-        states = data["states"].to(dev, f32)
-        ac = data["actions"].to(dev, f32)
-        true_masks = data["masks"].to(dev, f32)
-        masks = data["pred_masks"].to(dev, f32)
-        svg = cf.model == "svg"  # det (trainer.py:628-629) and copy (:606-607) have no prior: no KL term, no heatmap
-        heatmaps = data["heatmaps"].to(dev, f32) if getattr(cf, "model_use_heatmap", False) and svg else None
-        robot_name = np.array(data["robot"])
-        all_robots = sorted(set(robot_name))
-        bs = min(cf.test_batch_size, x.shape[1])
-        self.model.init_hidden(bs)
-        prefix = "autoreg" if autoregressive else "1step"
-        dontcare = "dontcare" in cf.reconstruction_loss or cf.black_robot_input
+        sn = self._snippet(data, autoregressive)
+        prefix = sn.prefix
         log, klog = [], []
-        x_pred = skip = None
-        for i in range(1, cf.n_eval):
-            x_j = x_pred if (autoregressive and i > 1) else x[i - 1]
-            m_j, r_j, a_j = masks[i - 1], states[i - 1], ac[i - 1]
-            m_i, r_i = masks[i], states[i]
-            if cf.last_frame_skip:
-                skip = None
-            m_in = torch.cat([m_j, m_i], 1) if cf.model_use_future_mask else m_j
-            r_in = (r_j, r_i) if cf.model_use_future_robot_state else r_j
-            hm_in = None
-            if heatmaps is not None:
-                hm_in = torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap else heatmaps[i - 1]
-            if cf.model == "copy":
-                x_pred = self.model(x_j, m_j, x[i], m_i)  # on the rollout's masks (`pred_masks`)
-            else:
-                if svg:
-                    x4, curr_skip, mu, logvar, mu_p, logvar_p = self.model.forward_maps(
-                        x_j, m_in, r_in, hm_in, a_j, True, r_i, skip, force_use_prior=True,
-                        zero_mask=m_j if dontcare else None)
-                else:
-                    x4, curr_skip = self.model.forward_maps(x_j, m_in, r_j, a_j, skip, zero_mask=m_j if dontcare else None)
-                x_pred = ops.Composite.apply(x4, x_j.contiguous())
-                if i <= cf.n_past:
-                    skip = curr_skip
-            tm = true_masks[i].contiguous()
-            rec = self._recon_loss(x_pred, x[i].contiguous(), tm)
+        for i, x_pred, latents, x_i, tm in self._prior_rollout(sn, autoregressive):
+            rec = self._recon_loss(x_pred, x_i, tm)
             log += [(f"{prefix}_recon_loss", rec[0]), (f"{prefix}_robot_loss", rec[1]), (f"{prefix}_world_loss", rec[2])]
-            p, s = masked_psnr_ssim(x_pred, x[i].contiguous(), tm)  # robot region blacked with the true mask
+            p, s = masked_psnr_ssim(x_pred, x_i, tm)  # robot region blacked with the true mask
             p = p.mean()
             log += [(f"{prefix}_psnr", p), (f"{prefix}_ssim", s)]
             if autoregressive:
                 klog += [(f"{i}_step_psnr", p), (f"{i}_step_ssim", s), (f"{i}_step_world_loss", rec[2])]
-            if len(all_robots) > 1:
-                for r in all_robots:
-                    idx = torch.from_numpy(np.nonzero(robot_name == r)[0]).to(dev)
-                    sub = ops.ReconLoss.apply(x_pred[idx].contiguous(), x[i][idx].contiguous(), tm[idx].contiguous(),
-                                              None, 0, 0.0)
-                    log += [(f"{prefix}_{r}_robot_loss", sub[1]), (f"{prefix}_{r}_world_loss", sub[2])]
-            if svg:
-                kl = ops.KLLoss.apply(mu, logvar, mu_p, logvar_p, bs)
+            for r, sub in self._per_robot_losses(x_pred, x_i, tm, sn.robot_name, sn.all_robots):
+                log += [(f"{prefix}_{r}_robot_loss", sub[1]), (f"{prefix}_{r}_world_loss", sub[2])]
+            if sn.svg:
+                kl = ops.KLLoss.apply(*latents, sn.bs)
                 log.append((f"{prefix}_kld", kl[0]))
         vals = torch.stack([t.reshape(()) for _, t in log + klog]).cpu().tolist()
         losses = defaultdict(float)
@@ -617,51 +640,19 @@ class PredictionTrainer(object):
         """`_eval_step(num_samples=S)`: the rollout of `_eval_step` on S B videos, one `ops.eval_frames` launch per frame."""
         from .metrics import table_scalars
         cf = self._config
-        dev, f32 = self._device, torch.float32
         if cf.model != "svg":
             raise ValueError("only --model svg draws samples")
-        x = data["images"].to(dev, f32)
-        states = data["states"].to(dev, f32)
-        ac = data["actions"].to(dev, f32)
-        true_masks = data["masks"].to(dev, f32)
-        masks = data["pred_masks"].to(dev, f32)
-        heatmaps = data["heatmaps"].to(dev, f32) if getattr(cf, "model_use_heatmap", False) else None
-        robot_name = np.array(data["robot"])
-        all_robots = sorted(set(robot_name))
-        bs = min(cf.test_batch_size, x.shape[1])
-        self.model.init_hidden(S * bs)
-        if S > 1:  # sample group s = rows [s bs, (s+1) bs)
-            rep = lambda t: t.repeat((1, S) + (1,) * (t.dim() - 2))
-            states, ac, masks = rep(states), rep(ac), rep(masks)
-            heatmaps = rep(heatmaps) if heatmaps is not None else None
-        frame_in = lambda i: x[i] if S == 1 else x[i].repeat(S, 1, 1, 1)
+        sn = self._snippet(data, autoregressive, S)
+        bs, prefix, robot_name, all_robots = sn.bs, sn.prefix, sn.robot_name, sn.all_robots
         n_steps = cf.n_eval - 1
-        H, W = x.shape[-2], x.shape[-1]
-        prefix = "autoreg" if autoregressive else "1step"
-        dontcare = "dontcare" in cf.reconstruction_loss or cf.black_robot_input
+        H, W = sn.x.shape[-2], sn.x.shape[-1]
         kind = self._loss_kind()
         rw = cf.robot_pixel_weight if "dontcare" in cf.reconstruction_loss else 0.0
-        table = torch.empty((n_steps, S * bs, 8), device=dev, dtype=f32)
+        table = torch.empty((n_steps, S * bs, 8), device=self._device, dtype=torch.float32)
         kls = []
-        x_pred = skip = None
-        for i in range(1, cf.n_eval):
-            x_j = x_pred if (autoregressive and i > 1) else frame_in(i - 1)
-            m_j, r_j, a_j = masks[i - 1], states[i - 1], ac[i - 1]
-            m_i, r_i = masks[i], states[i]
-            if cf.last_frame_skip:
-                skip = None
-            m_in = torch.cat([m_j, m_i], 1) if cf.model_use_future_mask else m_j
-            r_in = (r_j, r_i) if cf.model_use_future_robot_state else r_j
-            hm_in = None
-            if heatmaps is not None:
-                hm_in = torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap else heatmaps[i - 1]
-            x4, curr_skip, mu, logvar, mu_p, logvar_p = self.model.forward_maps(
-                x_j, m_in, r_in, hm_in, a_j, True, r_i, skip, force_use_prior=True, zero_mask=m_j if dontcare else None)
-            x_pred = ops.Composite.apply(x4, x_j.contiguous())
-            if i <= cf.n_past:
-                skip = curr_skip
+        for i, x_pred, (mu, logvar, mu_p, logvar_p), x_i, tm in self._prior_rollout(sn, autoregressive):
             # robot region blacked with, and the errors split by, the true mask
-            ops.eval_frames(x_pred, x[i], true_masks[i], kind, rw, S, out=table[i - 1])
+            ops.eval_frames(x_pred, x_i, tm, kind, rw, S, out=table[i - 1])
             for n in range(S):
                 sl = slice(n * bs, (n + 1) * bs)
                 kls.append(ops.KLLoss.apply(mu[sl], logvar[sl], mu_p[sl], logvar_p[sl], bs)[0])
@@ -712,37 +703,14 @@ class PredictionTrainer(object):
         `pred_masks`, and `out` stays unbound for experiments other than finetune_locobot without a learned model)."""
         cf = self._config
         num_samples = 3 if (cf.model == "svg" and "finetune" in cf.experiment) else 1
-        finetune = "finetune" in cf.experiment and (cf.model_use_mask or cf.model_use_robot_state)
-        if finetune and getattr(self, "robot_model", None) is None:
-            raise NotImplementedError(
-                "finetune_* evaluation rolls out on the robot model's states and masks (trainer.py:520-543): set "
-                "`trainer.robot_model` (the reference's LocobotAnalyticalModel, or robot_atlas.AtlasRobotModel)")
+        self._robot_windows()  # (a finetune_* run without a robot model is refused before its first window)
         batched = num_samples > 1 and os.environ.get("RAC_PREDICT_BATCH_SAMPLES", "1") == "1"
-        x = data["images"]
-        T = len(x)
+        T = len(data["images"])
         window = cf.n_eval
         sampled = [defaultdict(float) for _ in range(num_samples)]
         for i in range(floor(T / window)):
-            s, e = i * window, (i + 1) * window
-            batch = {"images": x[s:e], "states": data["states"][s:e], "actions": data["actions"][s:e - 1],
-                     "masks": data["masks"][s:e], "pred_masks": data["masks"][s:e], "robot": data["robot"]}
-            if "qpos" in data:
-                batch["qpos"] = data["qpos"][s:e]
-            if "folder" in data:
-                batch["folder"] = data["folder"]
-            if getattr(cf, "model_use_heatmap", False):
-                batch["heatmaps"] = data["heatmaps"][s:e]
-            if finetune:
-                # predicted states / masks drive the rollout, the true masks score and black the frames (trainer.py:1180-1202)
-                if getattr(cf, "preprocess_action", "raw") != "raw":
-                    batch["raw_actions"], batch["raw_states"] = data["raw_actions"][s:e - 1], data["raw_states"][s:e]
-                    batch["raw_low"], batch["raw_high"] = data["raw_low"], data["raw_high"]
-                batch["low"], batch["high"] = data["low"], data["high"]
-                out = self.robot_model.predict_batch(batch)
-                if getattr(cf, "model_use_heatmap", False):
-                    batch["states"], batch["pred_masks"], batch["heatmaps"] = out
-                else:
-                    batch["states"], batch["pred_masks"] = out
+            # predicted states / masks drive the rollout, the true masks score and black the frames (trainer.py:1180-1202)
+            batch = self._window_batch(data, i * window, (i + 1) * window, "pred_masks")
             if batched:
                 outs = self._predict_video(batch, num_samples=num_samples)
             else:
@@ -780,62 +748,22 @@ class PredictionTrainer(object):
         dicts that share one `true_imgs` array."""
         from .metrics import masked_psnr_ssim
         cf = self._config
-        dev, f32 = self._device, torch.float32
         S = int(num_samples)
-        x = data["images"].to(dev, f32)
-        states = data["states"].to(dev, f32)
-        ac = data["actions"].to(dev, f32)
-        true_masks = data["masks"].to(dev, f32)
-        masks = data["pred_masks"].to(dev, f32)
-        svg = cf.model == "svg"
-        if S > 1 and not svg:
-            raise ValueError("only --model svg draws samples")
-        heatmaps = data["heatmaps"].to(dev, f32) if getattr(cf, "model_use_heatmap", False) and svg else None
-        robot_name = np.array(data["robot"])
-        all_robots = sorted(set(robot_name))
-        bs = min(cf.test_batch_size, x.shape[1])
-        self.model.init_hidden(S * bs)
-        if S > 1:  # sample group s = rows [s bs, (s+1) bs)
-            rep = lambda t: t.repeat((1, S) + (1,) * (t.dim() - 2))
-            states, ac, masks = rep(states), rep(ac), rep(masks)
-            heatmaps = rep(heatmaps) if heatmaps is not None else None
-        frame_in = lambda i: x[i] if S == 1 else x[i].repeat(S, 1, 1, 1)
+        sn = self._snippet(data, autoregressive, S)
+        bs, prefix = sn.bs, sn.prefix
         n_steps = cf.n_eval - 1
-        H, W = x.shape[-2], x.shape[-1]
+        H, W = sn.x.shape[-2], sn.x.shape[-1]
         # gen frames of the S groups, then the true frames: one buffer, one copy to the host
-        frames = torch.empty(((S + 1) * bs, n_steps, H, W, 3), device=dev, dtype=torch.uint8)
+        frames = torch.empty(((S + 1) * bs, n_steps, H, W, 3), device=self._device, dtype=torch.uint8)
         gen_u8, true_u8 = frames[:S * bs], frames[S * bs:]
-        prefix = "autoreg" if autoregressive else "1step"
-        dontcare = "dontcare" in cf.reconstruction_loss or cf.black_robot_input
         log, klog = [], []  # (sample, name, scalar tensor); (sample, step, psnr, ssim, world_mse)
-        x_pred = skip = None
-        for i in range(1, cf.n_eval):
-            x_j = x_pred if (autoregressive and i > 1) else frame_in(i - 1)
-            m_j, r_j, a_j = masks[i - 1], states[i - 1], ac[i - 1]
-            m_i, r_i = masks[i], states[i]
-            x_i, tm = x[i].contiguous(), true_masks[i].contiguous()
-            if cf.last_frame_skip:
-                skip = None
-            m_in = torch.cat([m_j, m_i], 1) if cf.model_use_future_mask else m_j
-            r_in = (r_j, r_i) if cf.model_use_future_robot_state else r_j
-            hm_in = None
-            if heatmaps is not None:
-                hm_in = torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap else heatmaps[i - 1]
-            if cf.model == "copy":
-                x_pred = self.model(x_j, m_j, x_i, m_i)  # on the rollout's masks (`pred_masks`)
+        composite = lambda i, x4, x_j, x_i, tm: ops.predict_frames(x4, x_j, x_i, tm, gen_u8, true_u8, i - 1)
+        for i, x_pred, latents, x_i, tm in self._prior_rollout(sn, autoregressive, composite):
+            if cf.model == "copy":  # a finished frame: only the uint8 frames are written
                 ops.predict_frames(None, None, x_i, tm, gen_u8, true_u8, i - 1, pred=x_pred)
-            else:
-                if svg:
-                    x4, curr_skip, mu, logvar, mu_p, logvar_p = self.model.forward_maps(
-                        x_j, m_in, r_in, hm_in, a_j, True, r_i, skip, force_use_prior=True,
-                        zero_mask=m_j if dontcare else None)
-                else:
-                    x4, curr_skip = self.model.forward_maps(x_j, m_in, r_j, a_j, skip, zero_mask=m_j if dontcare else None)
-                x_pred = ops.predict_frames(x4, x_j, x_i, tm, gen_u8, true_u8, i - 1)
-                if i <= cf.n_past:
-                    skip = curr_skip
             for n in range(S):
-                xp = x_pred[n * bs:(n + 1) * bs]
+                sl = slice(n * bs, (n + 1) * bs)
+                xp = x_pred[sl]
                 rec = self._recon_loss(xp, x_i, tm)
                 log += [(n, f"{prefix}_recon_loss", rec[0]), (n, f"{prefix}_robot_loss", rec[1]),
                         (n, f"{prefix}_world_loss", rec[2])]
@@ -844,15 +772,10 @@ class PredictionTrainer(object):
                 log += [(n, f"{prefix}_psnr", p), (n, f"{prefix}_ssim", s)]
                 if autoregressive:
                     klog.append((n, i, p, s, rec[2]))
-                if len(all_robots) > 1:
-                    for r in all_robots:
-                        idx = torch.from_numpy(np.nonzero(robot_name == r)[0]).to(dev)
-                        sub = ops.ReconLoss.apply(xp[idx].contiguous(), x_i[idx].contiguous(), tm[idx].contiguous(),
-                                                  None, 0, 0.0)
-                        log += [(n, f"{prefix}_{r}_robot_loss", sub[1]), (n, f"{prefix}_{r}_world_loss", sub[2])]
-                if svg:
-                    sl = slice(n * bs, (n + 1) * bs)
-                    kl = ops.KLLoss.apply(mu[sl], logvar[sl], mu_p[sl], logvar_p[sl], bs)
+                for r, sub in self._per_robot_losses(xp, x_i, tm, sn.robot_name, sn.all_robots):
+                    log += [(n, f"{prefix}_{r}_robot_loss", sub[1]), (n, f"{prefix}_{r}_world_loss", sub[2])]
+                if sn.svg:
+                    kl = ops.KLLoss.apply(*(t[sl] for t in latents), bs)
                     log.append((n, f"{prefix}_kld", kl[0]))
         scalars = [t for _, _, t in log] + [t for e in klog for t in e[2:]]
         vals = torch.stack([t.reshape(()) for t in scalars]).cpu().tolist()
@@ -930,21 +853,11 @@ class PredictionTrainer(object):
             frames = [ops.ZeroRegion.apply(x_j.contiguous(), mask[0].contiguous()) if dontcare else x_j]
             skip = None
             for i in range(1, length):
-                m_j, m_i = mask[i - 1], mask[i]
-                if cf.last_frame_skip:
-                    skip = None
-                m_in = torch.cat([m_j, m_i], 1) if cf.model_use_future_mask else m_j
-                r_in = (states[i - 1], states[i]) if cf.model_use_future_robot_state else states[i - 1]
-                hm_in = None
-                if heatmaps is not None:
-                    hm_in = torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap else heatmaps[i - 1]
-                x4, curr_skip = self.model.forward_maps(x_j, m_in, r_in, hm_in, ac[i - 1], False, None, skip,
-                                                        zero_mask=m_j if dontcare else None)[:2]
+                x4, skip, _ = self._model_step(i, x_j, mask, states, ac, heatmaps, skip, posterior=False,
+                                               dontcare=dontcare)
                 x_pred = ops.Composite.apply(x4, x_j.contiguous())
-                if i <= cf.n_past:
-                    skip = curr_skip
                 x_j = x[i] if i < cf.n_past else x_pred
-                frames.append(ops.ZeroRegion.apply(x_pred, m_i.contiguous()) if dontcare else x_j)
+                frames.append(ops.ZeroRegion.apply(x_pred, mask[i].contiguous()) if dontcare else x_j)
             samples.append(torch.stack(frames))  # (length, b, 3, H, W)
         self.model.train(was_training)
         # one GIF frame per time step: b rows of [ground truth | sample 0 | sample 1 | sample 2]
