@@ -785,6 +785,26 @@ int rac_joint_batch(const double* states, const float* actions, const float* qpo
                     const int32_t* meta, const int32_t* index, const int32_t* start, float* qpos_out, float* states_out,
                     float* actions_out, int32_t N, int32_t Tmax, int32_t B, int32_t L, int32_t J, int32_t R, int32_t A,
                     int32_t state_infer, void* stream);
+/* The windows of one batch out of fp32 tables that live on the device, for up to RAC_GATHER_MAX_TABLES tables in ONE
+ * launch (data.py ResidentVideos: the video path's preprocessed states / actions / qpos / bounds; it replaces the
+ * per-key pinned upload + transpose of process_batch / DevicePrefetcher._upload for a `--device_resident` batch):
+ *   src[V][rows_stored][width] -> dst[rows][B][width],  dst[r][b][c] = src[index[b]][start[b] + r][c].
+ * rows = L for a per-frame table, L - 1 for a per-step table (actions); per_video != 0: rows = 1, `start` is ignored and
+ * dst is [B][width] (bounds, a camera row, a flag).  Any width >= 1, nothing beyond 4-byte alignment is assumed.  A pure
+ * copy with one writer per element: the same bits on every run.
+ * index[B], start[B] and length[V] (each video's stored frame count) live in device memory, so the entry point cannot see
+ * them: the CALLER checks 0 <= index < V and 0 <= start <= length - L before the upload, and the kernel clamps both
+ * (and the window into rows_stored) so that no value reads outside the tables.
+ * `tables` is a HOST array.  EINVAL, nothing launched: a NULL argument or table pointer, n_tables outside
+ * 1..RAC_GATHER_MAX_TABLES, V / B / L < 1, width < 1, rows not as above, rows_stored < rows. */
+#define RAC_GATHER_MAX_TABLES 8
+typedef struct rac_gather_table {
+  const float* src;
+  float* dst;
+  int32_t rows_stored, width, rows, per_video;
+} rac_gather_table;
+int rac_window_gather(const rac_gather_table* tables, int32_t n_tables, const int32_t* index, const int32_t* start,
+                      const int32_t* length, int32_t V, int32_t B, int32_t L, void* stream);
 /* Predicted against true masks, pred / truth [V][T][H][W] fp32 (set where nonzero), one workgroup per frame:
  *   counts[V][T][2] = {|pred & true|, |pred | true|}, exact int32, a fixed-order reduction;
  *   frames[T][V H][3 W] uint8 = per video one row [true | predicted | xor]: the two masks clamped to [0, 1] times 255

@@ -75,6 +75,14 @@ class HeatmapView(C.Structure):
                 ("reserved", i32)]
 
 
+GATHER_MAX_TABLES = 8  # RAC_GATHER_MAX_TABLES
+
+
+class GatherTable(C.Structure):
+    """struct rac_gather_table (include/rac_hip.h): one table of a rac_window_gather launch."""
+    _fields_ = [("src", vp), ("dst", vp), ("rows_stored", i32), ("width", i32), ("rows", i32), ("per_video", i32)]
+
+
 OPTIM_RMSPROP, OPTIM_SGD = 0, 1            # RAC_OPTIM_* rules
 OPTIM_NESTEROV, OPTIM_FIRST_STEP = 1, 2    # RAC_OPTIM_* flags
 
@@ -192,6 +200,7 @@ _SIGS = {
     "rac_mlp4_bwd": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
     "rac_mse_rows": [vp, vp, f32, vp, vp, i64, vp],
     "rac_joint_batch": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "rac_window_gather": [vp, i32, vp, vp, vp, i32, i32, i32, vp],
     "rac_mask_compare": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "rac_version": [],
     "rac_device_arch": [],

@@ -105,6 +105,9 @@ _COMPAT = [("stoch", B, False), ("multiview", B, False)]
 # MI355X additions (not in the reference)
 _NATIVE = [("ddp_bucket_mb", I, 64), ("cem_shard", B, True),
            ("device_images", B, False),  # image resize / crop / colour jitter of the data path on the device (data.py)
+           # a split's videos and preprocessed numerics live on the GPU; a batch is two launches (data.ResidentVideos)
+           ("device_resident", B, False),
+           ("device_resident_max_gb", F, 16.0),  # the largest split --device_resident may put on the device
            ("cem_exact_elites", I, 0),  # re-roll the M best candidates of an atlas pass with exactly rendered masks
            ("cem_shared_start", B, True),  # planner step 0: encode the (shared) start frame once, not per candidate
            ("ddp_shard_optimizer", B, False),  # DDP: reduce-scatter + Adam on 1/world slices + parameter all-gather

@@ -4,8 +4,12 @@
 //     preprocessing -- the imputed gripper command, `state_infer` actions, the gripper-force normalisation -- in the
 //     precision numpy / torch use on the host, so the batch has the bits of process_batch(collate(host items));
 //   * mask_compare_kernel counts intersection and union of predicted and true masks per frame and writes the
-//     [true | predicted | xor] comparison frames of the GIF.
-// Both are latency-sized: one thread per output element / one workgroup per frame, no atomics, fixed-order reductions.
+//     [true | predicted | xor] comparison frames of the GIF;
+//   * window_gather_kernel copies the windows of one batch out of up to 8 resident fp32 tables (the video path's
+//     preprocessed numerics, data.py ResidentVideos) into time-first outputs: a pure copy, one writer per element.
+// All are latency-sized: one thread per output element / one workgroup per frame, no atomics, fixed-order reductions.
+#include <algorithm>
+
 #include "rac_common.h"
 
 namespace rac {
@@ -85,6 +89,37 @@ __global__ void __launch_bounds__(256) joint_batch_kernel(JointSplit S, const in
   }
 }
 
+struct GatherTables {
+  rac_gather_table t[RAC_GATHER_MAX_TABLES];
+  long first[RAC_GATHER_MAX_TABLES + 1];  // element offsets of the tables in the launch's flat element range
+  int n;
+};
+
+// dst[r][b][c] = src[v][s + r][c] per table, v = index[b], s = start[b] (0 for a per-video table).  index, start and
+// length were checked on the host; the clamps keep any value inside the tables regardless.  Scalar 4-byte accesses:
+// widths such as 5 and 7 leave no wider alignment.
+__global__ void __launch_bounds__(256) window_gather_kernel(GatherTables G, const int* __restrict__ index,
+                                                            const int* __restrict__ start, const int* __restrict__ length,
+                                                            int V, int B, int L) {
+  const long total = G.first[G.n];
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    int k = 0;
+    while (k + 1 < G.n && e >= G.first[k + 1]) ++k;
+    const rac_gather_table T = G.t[k];
+    const long i = e - G.first[k];
+    const int c = (int)(i % T.width);
+    const int b = (int)((i / T.width) % B);
+    const int r = (int)(i / ((long)T.width * B));
+    const int v = min(max(index[b], 0), V - 1);
+    int s = 0;
+    if (!T.per_video) {
+      const int len = max(length[v], L);
+      s = min(min(max(start[b], 0), len - L), T.rows_stored - T.rows);
+    }
+    T.dst[i] = T.src[((long)v * T.rows_stored + s + r) * T.width + c];
+  }
+}
+
 // One workgroup per (video, time step) frame of H x W pixels.  counts[frame] = {|pred & true|, |pred | true|} (a mask is
 // set where it is nonzero); frames[t][v H + y][x + {0, W, 2 W}] = true, predicted (clamped to [0, 1], times 255,
 // truncated) and 255 where exactly one of them is set.
@@ -149,6 +184,33 @@ int rac_joint_batch(const double* states, const float* actions, const float* qpo
   hipLaunchKernelGGL(joint_batch_kernel, dim3(cdiv(total, 256)), dim3(256), 0, ST(stream), S, index, start, qpos_out,
                      states_out, actions_out, B, L, state_infer);
   return check_launch("rac_joint_batch");
+}
+
+int rac_window_gather(const rac_gather_table* tables, int32_t n_tables, const int32_t* index, const int32_t* start,
+                      const int32_t* length, int32_t V, int32_t B, int32_t L, void* stream) {
+  RAC_REQUIRE(tables && index && start && length, "rac_window_gather: NULL argument");
+  RAC_REQUIRE(n_tables >= 1 && n_tables <= RAC_GATHER_MAX_TABLES, "rac_window_gather: %d tables, 1..%d in one launch",
+              n_tables, RAC_GATHER_MAX_TABLES);
+  RAC_REQUIRE(V >= 1 && B >= 1 && L >= 1, "rac_window_gather: V %d, B %d, L %d must be >= 1", V, B, L);
+  GatherTables G = {};
+  G.n = n_tables;
+  G.first[0] = 0;
+  for (int k = 0; k < n_tables; ++k) {
+    const rac_gather_table& t = tables[k];
+    RAC_REQUIRE(t.src && t.dst, "rac_window_gather: table %d has a NULL pointer", k);
+    RAC_REQUIRE(t.width >= 1 && t.rows >= 1 && t.rows_stored >= t.rows,
+                "rac_window_gather: table %d: width %d, %d rows of %d stored", k, t.width, t.rows, t.rows_stored);
+    RAC_REQUIRE(t.per_video ? t.rows == 1 : (t.rows == L || t.rows == L - 1),
+                "rac_window_gather: table %d: %d rows for a window of %d (L or L - 1; 1 for a per-video table)", k, t.rows,
+                L);
+    G.t[k] = t;
+    G.first[k + 1] = G.first[k] + (long)t.rows * B * t.width;
+    RAC_REQUIRE((long)V * t.rows_stored * t.width < (1L << 31) && G.first[k + 1] < (1L << 31),
+                "rac_window_gather: table %d is too large (V %d x %d rows x %d)", k, V, t.rows_stored, t.width);
+  }
+  const int blocks = (int)std::min<long>(cdiv(G.first[n_tables], 256), 1024);
+  hipLaunchKernelGGL(window_gather_kernel, dim3(blocks), dim3(256), 0, ST(stream), G, index, start, length, V, B, L);
+  return check_launch("rac_window_gather");
 }
 
 int rac_mask_compare(const float* pred, const float* truth, int32_t* counts, uint8_t* frames, int32_t V, int32_t T,

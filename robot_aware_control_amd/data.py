@@ -20,10 +20,15 @@ What is different, for a trainer that consumes ~2 800 frames/s per GPU:
     `rac_image_pipeline` launch on the prefetcher's stream writes the time-first fp32 `images` / `masks`;
   * `--model_use_heatmap True`: an item carries its bounds and its camera (`heatmap_view`, a row of numbers from
     heatmaps.CameraTable) and `process_batch` / the prefetcher add the time-first `heatmaps` of the whole batch with one
-    `rac_eef_heatmaps` launch on the stream they already use (the reference's dataset raises under this flag).
+    `rac_eef_heatmaps` launch on the stream they already use (the reference's dataset raises under this flag);
+  * `experiment_loaders` gives every `--experiment` of the reference's trainer its own split (trainer.py:899-947), and
+    `--device_resident True` (off by default) keeps such a split on the GPU: `ResidentVideos` holds every stored video
+    and the preprocessed numerics, the loader only draws (`ResidentDataset`), and a batch is `rac_image_pipeline` on the
+    resident frames plus `rac_window_gather` for the numerics behind an upload of the jobs and the (index, start) pairs.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 import pickle
 import random
@@ -439,63 +444,91 @@ class RoboNetDataset(data.Dataset):
             actions = imputed_gripper_actions(actions, traj["states"][:][1:, -1], g_low, g_high).astype(np.float32)
         return actions[start:end]
 
-    def __getitem__(self, idx):
-        if idx in self._memory:
-            return self._memory[idx]
+    def stored_numerics(self, traj, pipe, s, e):
+        """What the numeric half reads of frames [s, e) of an open trajectory: (raw_low, raw_high, raw_states (e - s, R),
+        raw_actions (e - s - 1, A), qpos (e - s, J), robot)."""
         cf = self._config
-        name, viewpoint = self._traj_names[idx], self._traj_robots[idx]
-        path = os.path.join(self._data_root, name)
-        pipe = self.pipeline(viewpoint)
-        with open_trajectory(path) as traj:
-            frames_key = "observations" if "observations" in traj else "frames"
-            assert frames_key in traj, path
-            masks_key = "masks" if "masks" in traj else "mask"
-            s, e = self._window(traj[frames_key].shape[0], path)
-            frames = traj[frames_key][s:e]
-            masks = traj[masks_key][s:e]
-            masks = (masks != 0).astype(np.uint8) if self._device_images else masks.astype(np.float32)
-            raw_low, raw_high = pipe.view.bounds(traj)
-            raw_states = fit_width(traj["states"][s:e].astype(np.float32), cf.robot_dim)
-            raw_actions = self.read_actions(traj, s, e - 1, raw_low[4], raw_high[4])
-            qpos = fit_width(traj["qpos"][s:e].astype(np.float32), cf.robot_joint_dim)
-            robot = traj.attrs["robot"] if "robot" in traj.attrs else pipe.view.default_robot
-            robot = robot.decode() if isinstance(robot, bytes) else str(robot)
-        if not len(frames) == len(raw_states) == len(raw_actions) + 1 == len(masks):
-            raise AssertionError(f"{path}, {frames.shape}, {raw_states.shape}, {raw_actions.shape}, {masks.shape}")
+        raw_low, raw_high = pipe.view.bounds(traj)
+        raw_states = fit_width(traj["states"][s:e].astype(np.float32), cf.robot_dim)
+        raw_actions = self.read_actions(traj, s, e - 1, raw_low[4], raw_high[4])
+        qpos = fit_width(traj["qpos"][s:e].astype(np.float32), cf.robot_joint_dim)
+        robot = traj.attrs["robot"] if "robot" in traj.attrs else pipe.view.default_robot
+        robot = robot.decode() if isinstance(robot, bytes) else str(robot)
+        return raw_low, raw_high, raw_states, raw_actions, qpos, robot
+
+    def numerics(self, pipe, stored, folder, path):
+        """The numeric keys of an item from `stored_numerics` of its frames: states, actions, qpos (+ low / high /
+        heatmap_view, raw_*, high_movement as the flags ask).  Every step works row by row, so the rows of a window are
+        the same bits whether the window or the whole video is handed in (the device-resident split relies on it)."""
+        cf = self._config
+        raw_low, raw_high, raw_states, raw_actions, qpos, robot = stored
         if self._heatmaps and pipe.camera:
             # the heatmap projects WORLD-frame positions; the camera strategies normalise the states in the camera frame
             # (the reference's own open TODO, robonet_dataset.py:132-135 "need to account for camera space state")
             raise NotImplementedError(f"model_use_heatmap with preprocess_action={cf.preprocess_action!r}: the states are "
                                       f"in the camera frame, the heatmap needs them in the world frame")
         low, high = pipe.bounds(raw_low, raw_high)
-        if self._device_images:
-            if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[-1] != 3:
-                raise ValueError(f"{path}: device_images needs uint8 (T,H,W,3) frames, got {frames.dtype} {frames.shape}")
-            pictures = {"frames": torch.from_numpy(np.ascontiguousarray(frames))}
-            mask_keys = {"raw_masks": torch.from_numpy(masks), "image_params": self._images.draw()}
-        else:
-            images, masks = self._images(frames, masks)
-            pictures, mask_keys = {"images": images}, {"masks": masks}
         states = pipe.states(raw_states, low, high)
         actions = pipe.actions(states, raw_actions, low, high)
-        folder = os.path.basename(os.path.dirname(name))
-        item = {**pictures, "states": states, "actions": actions, **mask_keys, "robot": robot, "folder": folder,
-                "file_path": path, "idx": idx, "qpos": qpos}
+        out = {"states": states, "actions": actions, "qpos": qpos}
         if self._heatmaps:  # what rac_eef_heatmaps needs of this video: its bounds and its camera
-            item["low"], item["high"] = low, high
-            item["heatmap_view"] = self.camera_table().view_row(robot, folder, cf.image_height, cf.image_width).copy()
+            out["low"], out["high"] = low, high
+            out["heatmap_view"] = self.camera_table().view_row(robot, folder, cf.image_height, cf.image_width).copy()
         if "finetune" in cf.experiment:  # the robot model of finetune_* windows needs the bounds (:148-166)
-            item["low"], item["high"] = low, high
+            out["low"], out["high"] = low, high
             if cf.preprocess_action != "raw":
                 if not pipe.camera:
                     raise NotImplementedError
                 world = raw_states.copy()  # world-frame states, normalised by the file's own bounds
                 world[:, :3] = normalize(world[:, :3], raw_low[:3], raw_high[:3])
                 world[:, 4] = normalize(world[:, 4], raw_low[4], raw_high[4])
-                item.update(raw_low=raw_low, raw_high=raw_high, raw_actions=raw_actions.copy(), raw_states=world)
+                out.update(raw_low=raw_low, raw_high=raw_high, raw_actions=raw_actions.copy(), raw_states=world)
         if self._movement is not None:
-            item["high_movement"] = self._movement[folder][path]
-        return item
+            out["high_movement"] = self._movement[folder][path]
+        return out
+
+    def __getitem__(self, idx):
+        if idx in self._memory:
+            return self._memory[idx]
+        name, viewpoint = self._traj_names[idx], self._traj_robots[idx]
+        path = os.path.join(self._data_root, name)
+        pipe = self.pipeline(viewpoint)
+        with open_trajectory(path) as traj:
+            frames_key, masks_key = picture_keys(traj, path)
+            s, e = self._window(traj[frames_key].shape[0], path)
+            frames = traj[frames_key][s:e]
+            masks = traj[masks_key][s:e]
+            masks = (masks != 0).astype(np.uint8) if self._device_images else masks.astype(np.float32)
+            stored = self.stored_numerics(traj, pipe, s, e)
+        raw_states, raw_actions, robot = stored[2], stored[3], stored[5]
+        if not len(frames) == len(raw_states) == len(raw_actions) + 1 == len(masks):
+            raise AssertionError(f"{path}, {frames.shape}, {raw_states.shape}, {raw_actions.shape}, {masks.shape}")
+        folder = os.path.basename(os.path.dirname(name))
+        if self._heatmaps and pipe.camera:
+            self.numerics(pipe, stored, folder, path)  # (raises, before anything is drawn)
+        if self._device_images:
+            check_raw_frames(frames, path)
+            pictures = {"frames": torch.from_numpy(np.ascontiguousarray(frames))}
+            mask_keys = {"raw_masks": torch.from_numpy(masks), "image_params": self._images.draw()}
+        else:
+            images, masks = self._images(frames, masks)
+            pictures, mask_keys = {"images": images}, {"masks": masks}
+        rest = self.numerics(pipe, stored, folder, path)
+        return {**pictures, "states": rest.pop("states"), "actions": rest.pop("actions"), **mask_keys, "robot": robot,
+                "folder": folder, "file_path": path, "idx": idx, "qpos": rest.pop("qpos"), **rest}
+
+
+def picture_keys(traj, path):
+    """The names of a trajectory file's frames and masks (RoboNet's `frames` / `mask`, the authors' rigs'
+    `observations` / `masks`)."""
+    frames_key = "observations" if "observations" in traj else "frames"
+    assert frames_key in traj, path
+    return frames_key, "masks" if "masks" in traj else "mask"
+
+
+def check_raw_frames(frames, path):
+    if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[-1] != 3:
+        raise ValueError(f"{path}: device_images needs uint8 (T,H,W,3) frames, got {frames.dtype} {frames.shape}")
 
 
 # --------------------------------------------------------------------------- #
@@ -543,6 +576,8 @@ def collate(items):
     rigs), so the bytes of all `frames` go into ONE flat uint8 buffer, all `raw_masks` into another, and `image_jobs`
     (B, sizeof(rac_image_job)) uint8 holds one job per video: its byte offsets into the two buffers, its (Hs, Ws) and
     its `ImageParams`; `image_shape` = (T, h, w)."""
+    if isinstance(items[0], ResidentChoice):
+        return items[0].store.collate(items)
     if "frames" not in items[0]:
         return data.default_collate(items)
     out = data.default_collate([{k: v for k, v in it.items() if k not in ("frames", "raw_masks", "image_params")}
@@ -571,10 +606,13 @@ def _image_jobs(batch):
     """The job records of a collated device_images batch, checked against the buffers they index."""
     jobs = batch["image_jobs"].numpy().reshape(-1).view(IMAGE_JOB)
     T, h, w = (int(v) for v in batch["image_shape"])
+    store = batch.get(RESIDENT_KEY)  # (a resident batch indexes its store's buffers)
+    n_frames, n_masks = ((store.frames.numel(), store.raw_masks.numel()) if store is not None
+                         else (batch["frames"].numel(), batch["raw_masks"].numel()))
     for j in jobs:
         n = T * int(j["Hs"]) * int(j["Ws"])
         ok = (j["Hs"] >= 1 and j["Ws"] >= 1 and j["frame_offset"] >= 0 and j["mask_offset"] >= 0
-              and j["frame_offset"] + 3 * n <= batch["frames"].numel() and j["mask_offset"] + n <= batch["raw_masks"].numel()
+              and j["frame_offset"] + 3 * n <= n_frames and j["mask_offset"] + n <= n_masks
               and j["th"] >= 1 and j["tw"] >= 1 and j["top"] >= 0 and j["left"] >= 0
               and j["top"] + j["th"] <= h and j["left"] + j["tw"] <= w and sorted(j["order"]) == [0, 1, 2, 3])
         if not ok:
@@ -608,6 +646,10 @@ def job_video(j, frames, masks, T):
             masks[j["mask_offset"]:j["mask_offset"] + n].reshape(T, Hs, Ws))
 
 
+def _pinned(t):
+    return t if t.is_pinned() else t.pin_memory()
+
+
 def device_images(batch, device):
     """Time-first `images` (T,B,3,h,w) / `masks` (T,B,1,h,w) of a collated device_images batch on `device`: the raw
     buffers and the job array are uploaded and ONE `rac_image_pipeline` launch does the rest, all on the current
@@ -637,12 +679,38 @@ def create_loaders(config):
     on identical batches and the gradient all-reduce would average copies of one gradient."""
     X_train, X_test, y_train, y_test = split_files(config)
     world, rank = _dist_info()
-    on_device = getattr(config, "device_images", False)
-    train_data = RoboNetDataset(X_train, y_train, config, augment_img=getattr(config, "img_augmentation", False),
-                                rng_seed=config.seed + rank if world > 1 else None, device_images=on_device)
-    test_data = RoboNetDataset(X_test, y_test, config, device_images=on_device)
-    common = dict(num_workers=config.data_threads, drop_last=False, pin_memory=True, collate_fn=collate,
-                  persistent_workers=config.data_threads > 0)
+    return _split_loaders(config, (X_train, y_train), (X_test, y_test))
+
+
+def _dataset(files, labels, config, augment=False, rng_seed=None):
+    """The dataset of one split under the config's flags: `RoboNetDataset` with `--device_images` honoured, behind a
+    `ResidentDataset` over its device-resident store with `--device_resident True`."""
+    resident = getattr(config, "device_resident", False)
+    if resident and getattr(config, "preload_ram", False):
+        raise ValueError("--preload_ram True and --device_resident True: the split is kept either in host memory or on the "
+                         "device, not both")
+    ds = RoboNetDataset(files, labels, config, augment_img=augment and getattr(config, "img_augmentation", False),
+                        rng_seed=rng_seed, device_images=resident or getattr(config, "device_images", False))
+    if resident:
+        ds = ResidentDataset(ds, ResidentVideos(ds, config.device, getattr(config, "device_resident_max_gb", 16.0)))
+    return ds
+
+
+def _threads(ds, config):
+    """A resident dataset only draws numbers: its loader never has workers (they would each copy the random streams)."""
+    return 0 if isinstance(ds, ResidentDataset) else config.data_threads
+
+
+def _split_loaders(config, train, test, test_shuffle=True):
+    """(train loader, test loader) over (files, labels) pairs, by `create_loaders`' conventions: the train split
+    augmented under `--img_augmentation`, sharded by a DistributedSampler under torch.distributed with a window-start
+    seed per rank, both loaders shuffled by generators seeded with the config seed."""
+    world, rank = _dist_info()
+    train_data = _dataset(*train, config, augment=True, rng_seed=config.seed + rank if world > 1 else None)
+    test_data = _dataset(*test, config)
+    threads = _threads(train_data, config)
+    common = dict(num_workers=threads, drop_last=False, pin_memory=True, collate_fn=collate,
+                  persistent_workers=threads > 0)
     if world > 1:
         sampler = data.distributed.DistributedSampler(train_data, num_replicas=world, rank=rank, shuffle=True,
                                                       seed=config.seed)
@@ -650,7 +718,7 @@ def create_loaders(config):
     else:
         train = data.DataLoader(train_data, batch_size=config.batch_size, shuffle=True,
                                 generator=torch.Generator().manual_seed(config.seed), **common)
-    test = data.DataLoader(test_data, batch_size=config.test_batch_size, shuffle=True,
+    test = data.DataLoader(test_data, batch_size=config.test_batch_size, shuffle=test_shuffle,
                            generator=torch.Generator().manual_seed(config.seed), **common)
     return train, test
 
@@ -677,9 +745,10 @@ def _locobot_files(config):
 
 
 def _plain_loader(ds, config, batch_size):
-    return data.DataLoader(ds, num_workers=config.data_threads, batch_size=batch_size, shuffle=True, drop_last=False,
+    threads = _threads(ds, config)
+    return data.DataLoader(ds, num_workers=threads, batch_size=batch_size, shuffle=True, drop_last=False,
                            pin_memory=True, generator=torch.Generator().manual_seed(config.seed), collate_fn=collate,
-                           persistent_workers=config.data_threads > 0)
+                           persistent_workers=threads > 0)
 
 
 MOVEMENT_FILE = "obj_movement.pkl"  # per viewpoint folder: {file path: high-movement flag}, written by movement.py
@@ -720,8 +789,7 @@ def create_movement_loader(config, n_files: int = 4000):
     """Loader over the high-movement videos only (robonet_dataloaders.py:295-327): up to 4000 files flagged true in
     their viewpoint folder's obj_movement.pkl, no augmentation, batches of `config.batch_size`."""
     files, labels = movement_files(config, n_files)
-    ds = RoboNetDataset(files, labels, config, device_images=getattr(config, "device_images", False))
-    return _plain_loader(ds, config, config.batch_size)
+    return _plain_loader(_dataset(files, labels, config), config, config.batch_size)
 
 
 def create_transfer_loader(config, n_files: int = 400):
@@ -730,21 +798,362 @@ def create_transfer_loader(config, n_files: int = 400):
     files, labels = _locobot_files(config)
     if not files:
         return None
-    ds = RoboNetDataset(files[:n_files], labels[:n_files], config, augment_img=getattr(config, "img_augmentation", False),
-                        device_images=getattr(config, "device_images", False))
-    return _plain_loader(ds, config, config.batch_size)
+    return _plain_loader(_dataset(files[:n_files], labels[:n_files], config, augment=True), config, config.batch_size)
 
 
 def create_finetune_loaders(config):
     """`--experiment finetune_locobot`: finetune_num_test files for testing, the next finetune_num_train for training
     (locobot_singleview_dataloader.py:12-57)."""
     files, labels = _locobot_files(config)
-    n_test, n_train = config.finetune_num_test, config.finetune_num_train
-    on_device = getattr(config, "device_images", False)
-    train = RoboNetDataset(files[n_test:n_test + n_train], labels[n_test:n_test + n_train], config,
-                           augment_img=getattr(config, "img_augmentation", False), device_images=on_device)
-    test = RoboNetDataset(files[:n_test], labels[:n_test], config, device_images=on_device)
-    return _plain_loader(train, config, config.batch_size), _plain_loader(test, config, config.test_batch_size)
+    return _head_split_loaders(config, files, labels, config.finetune_num_test, config.finetune_num_train)
+
+
+def _head_split_loaders(config, files, labels, n_test, n_train, test_shuffle=True):
+    """The first `n_test` files test, the next `n_train` train (the finetune_* and locobot rules)."""
+    return _split_loaders(config, (files[n_test:n_test + n_train], labels[n_test:n_test + n_train]),
+                          (files[:n_test], labels[:n_test]), test_shuffle)
+
+
+# --------------------------------------------------------------------------- #
+# one pair of loaders per --experiment (the reference trainer's _setup_data, trainer.py:899-947)
+# --------------------------------------------------------------------------- #
+# sawyer_dataloaders.py:13-16: the multiview experiment trains on every sawyer viewpoint but one and transfers to that one
+SAWYER_MULTIVIEW_TRAIN_DIRS = [d for d in SAWYER_TRAIN_DIRS if d != "sudri2_c1"]
+SAWYER_UNSEEN_VIEW = "sudri2_c1"
+
+
+def high_movement_files(config, subdir, view):
+    """The trajectory files of <data_root>/<subdir>/<view> in which the world moves, sorted by path and shuffled after
+    `random.seed(config.seed)` (sawyer_dataloaders.py:18-35, widowx_dataloaders.py:10-28).  With `--world_error_dict` the
+    filter is the reference's pickle {path: [{"high_error": bool}, ...]}: a file stays if any entry is true.  Without it,
+    the folder's own obj_movement.pkl decides (`load_movement_table`)."""
+    folder = os.path.join(config.data_root, subdir, view)
+    paths = [d.path for d in os.scandir(folder) if d.is_file() and d.path.lower().endswith(TRAJ_EXTENSIONS)]
+    if getattr(config, "world_error_dict", None):
+        with open(config.world_error_dict, "rb") as f:
+            motion_info = pickle.load(f)
+        paths = [p for p in paths if any(x["high_error"] for x in motion_info[p])]
+    else:
+        table = load_movement_table(folder)
+        paths = [p for p in paths if bool(table.get(p, False))]
+    paths = sorted(paths)
+    random.seed(config.seed)
+    random.shuffle(paths)
+    return paths
+
+
+def _view_finetune_loaders(config, subdir, view, label):
+    files = high_movement_files(config, subdir, view)
+    return _head_split_loaders(config, files, [label] * len(files), config.finetune_num_test, config.finetune_num_train)
+
+
+def create_widowx_finetune_loaders(config):
+    """`--experiment finetune_widowx` (widowx_dataloaders.py:10-63): the high-movement videos of widowx1_c0."""
+    return _view_finetune_loaders(config, "widowx_views", "widowx1_c0", "widowx_widowx1_c0")
+
+
+def create_sawyer_finetune_loaders(config):
+    """`--experiment finetune_sawyer_view` (sawyer_dataloaders.py:18-70): the high-movement videos of the sawyer
+    viewpoint the multiview experiment never trains on."""
+    return _view_finetune_loaders(config, "sawyer_views", SAWYER_UNSEEN_VIEW, "sawyer_" + SAWYER_UNSEEN_VIEW)
+
+
+def create_sawyer_loaders(config):
+    """`--experiment train_sawyer_multiview` (sawyer_dataloaders.py:126-190): the sawyer training viewpoints, one sort
+    and seeded shuffle, `train_test_split` without stratification."""
+    from sklearn.model_selection import train_test_split
+    fl = _robot_files(config, "sawyer_views", SAWYER_MULTIVIEW_TRAIN_DIRS, "sawyer")
+    X_train, X_test, y_train, y_test = train_test_split([x[0] for x in fl], [x[1] for x in fl],
+                                                        test_size=1 - config.train_val_split,
+                                                        random_state=np.random.RandomState(config.seed))
+    return _split_loaders(config, (X_train, y_train), (X_test, y_test))
+
+
+def create_sawyer_transfer_loader(config, n_files: int = 500):
+    """Zero-shot set of `train_sawyer_multiview` (sawyer_dataloaders.py:83-124): the first 500 high-movement videos of the
+    unseen viewpoint, of those the train part of `train_test_split`; no augmentation, batches of `test_batch_size`."""
+    from sklearn.model_selection import train_test_split
+    files = high_movement_files(config, "sawyer_views", SAWYER_UNSEEN_VIEW)[:n_files]
+    labels = ["sawyer_" + SAWYER_UNSEEN_VIEW] * len(files)
+    X_train, _, y_train, _ = train_test_split(files, labels, test_size=1 - config.train_val_split,
+                                              random_state=np.random.RandomState(config.seed))
+    return _plain_loader(_dataset(X_train, y_train, config), config, config.test_batch_size)
+
+
+def create_locobot_loaders(config, n_test: int = 200, n_train: int = 3000):
+    """`--experiment train_locobot_singleview` (locobot_singleview_dataloader.py:97-146): 200 videos test, the next 3000
+    train; the test loader walks its files in order."""
+    files, labels = _locobot_files(config)
+    return _head_split_loaders(config, files, labels, n_test, n_train, test_shuffle=False)
+
+
+def create_locobot_table_loaders(config, n_test: int = 1000, n_train: int = 10000):
+    """`--experiment train_locobot_table` (locobot_table_dataloaders.py:95-144): <data_root>/locobot_table_views/c0, 1000
+    videos test, the next 10000 train."""
+    folder = os.path.join(config.data_root, "locobot_table_views", "c0")
+    files = sorted(d.path for d in os.scandir(folder) if d.is_file() and d.path.lower().endswith(TRAJ_EXTENSIONS))
+    random.seed(config.seed)
+    random.shuffle(files)
+    return _head_split_loaders(config, files, ["locobot_c0"] * len(files), n_test, n_train)
+
+
+EXPERIMENT_LOADERS = {  # --experiment -> (train / test loaders, transfer loader or None)
+    "train_robonet": (create_loaders, create_transfer_loader),
+    "train_sawyer_multiview": (create_sawyer_loaders, create_sawyer_transfer_loader),
+    "finetune_sawyer_view": (create_sawyer_finetune_loaders, None),
+    "finetune_widowx": (create_widowx_finetune_loaders, None),
+    "train_locobot_singleview": (create_locobot_loaders, None),
+    "finetune_locobot": (create_finetune_loaders, None),
+    "train_locobot_table": (create_locobot_table_loaders, None),
+    # the stale value of published command lines (config.py: accepted, not in the reference's parser): the RoboNet
+    # split it has always run on here, without the transfer set
+    "singlerobot": (create_loaders, None),
+}
+
+
+def experiment_loaders(config, transfer: bool = True):
+    """(train loader, test loader, transfer loader or None) of `config.experiment`, chosen as the reference's trainer
+    chooses them (trainer.py:899-947); `transfer=False` leaves the transfer loader unbuilt.  An experiment it has no loaders for raises NotImplementedError, as there
+    (`train_locobot_pick` among them: its simulated-pick dataset is not part of this package)."""
+    if config.experiment not in EXPERIMENT_LOADERS:
+        raise NotImplementedError(config.experiment)
+    loaders, transfer_loader = EXPERIMENT_LOADERS[config.experiment]
+    train, test = loaders(config)
+    return train, test, (transfer_loader(config) if transfer and transfer_loader is not None else None)
+
+
+# --------------------------------------------------------------------------- #
+# --device_resident True: a split that lives on the device
+# --------------------------------------------------------------------------- #
+RESIDENT_KEY = "resident"                                     # of a collated resident batch: its ResidentVideos
+RESIDENT_BATCH_KEYS = (RESIDENT_KEY, "image_jobs", "image_shape", "index", "start")  # gone once the batch is made
+WINDOW_TABLES = ("states", "actions", "qpos", "raw_states", "raw_actions")            # (V, rows, width): a window each
+STEP_TABLES = ("actions", "raw_actions")                                              # (a row per step: one fewer)
+VIDEO_TABLES = ("low", "high", "raw_low", "raw_high")                                 # (V, width): one row per video
+
+
+class ResidentChoice(NamedTuple):
+    """What is drawn at random for one item of a resident split: the video, its window start and its `ImageParams`."""
+    idx: int
+    start: int
+    params: ImageParams
+    store: "ResidentVideos"
+
+
+class ResidentVideos:
+    """One split of a `RoboNetDataset` on the device, built once:
+      * `frames` / `raw_masks`: every file's WHOLE stored video (uint8 (L_v, Hs, Ws, 3)) and `mask != 0` back to back in
+        two flat uint8 buffers; the byte offsets, `shapes` (L_v, Hs, Ws) and the strings stay on the host;
+      * `tables`: the numeric keys of an item, computed once per file by the dataset's `NumericPipeline` over the whole
+        video, as fp32 tables padded to the longest video: states (V, Lmax, R), actions (V, Lmax - 1, A), qpos
+        (V, Lmax, J), low / high (V, 5) (+ raw_* under finetune_* with a camera strategy); `lengths` int32 (V,);
+      * `host_rows`, on the host: `heatmap_view` (17 float64 numbers per video under --model_use_heatmap: the rows are
+        fp64 and rac_eef_heatmaps takes records packed on the host), `high_movement` under --load_movement_info (a host
+        tensor in the batch dict either way) and bounds that a file stores as float64.
+    A batch is then `collate` of B `ResidentChoice`s -> `device_batch`: the job array and an (index, start) pair per
+    sample are uploaded, `rac_image_pipeline` reads the frames in place and `rac_window_gather` copies the windows."""
+
+    def __init__(self, dataset: RoboNetDataset, device, max_gb: float = 16.0):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.RacError(f"--device_resident True keeps the split on a GPU, not on {self.device} (no CPU fallback)")
+        self.window = dataset._video_length
+        paths, shapes = [], []
+        for name in dataset._traj_names:  # sizes first: nothing is allocated for a split that does not fit
+            path = os.path.join(dataset._data_root, name)
+            with open_trajectory(path) as traj:
+                fk, mk = picture_keys(traj, path)
+                shape, mshape = tuple(traj[fk].shape), tuple(traj[mk].shape)
+            if len(shape) != 4 or shape[3] != 3 or mshape != shape[:3] or shape[0] < self.window:
+                raise ValueError(f"{path}: frames {shape}, masks {mshape} for a window of {self.window} (T,H,W,3) frames")
+            paths.append(path)
+            shapes.append(shape[:3])
+        if not paths:
+            raise ValueError("ResidentVideos: an empty split")
+        self.paths, self.shapes = paths, np.array(shapes, np.int64)
+        pixels = self.shapes.prod(1)
+        self.mask_offsets = np.concatenate([[0], np.cumsum(pixels)])
+        self.frame_offsets = 3 * self.mask_offsets
+        cf = dataset._config
+        V, Lmax = len(paths), int(self.shapes[:, 0].max())
+        numeric = 4 * V * Lmax * (2 * (cf.robot_dim + cf.action_dim) + cf.robot_joint_dim + 20)  # (an upper bound)
+        need = 4 * int(self.mask_offsets[-1]) + numeric
+        if need > max_gb * 2 ** 30:
+            raise ValueError(f"the split needs {need / 2 ** 30:.2f} GB on the device, above --device_resident_max_gb "
+                             f"{max_gb:g}: raise the flag or train from the loaders")
+        self.frames = torch.empty(int(self.frame_offsets[-1]), dtype=torch.uint8, device=self.device)
+        self.raw_masks = torch.empty(int(self.mask_offsets[-1]), dtype=torch.uint8, device=self.device)
+        rows, self.robots, self.folders = [], [], []
+        for i, (path, name, viewpoint) in enumerate(zip(paths, dataset._traj_names, dataset._traj_robots)):
+            pipe = dataset.pipeline(viewpoint)
+            folder = os.path.basename(os.path.dirname(name))
+            with open_trajectory(path) as traj:
+                fk, mk = picture_keys(traj, path)
+                frames, masks = traj[fk][:], traj[mk][:]
+                stored = dataset.stored_numerics(traj, pipe, 0, len(frames))
+            check_raw_frames(frames, path)
+            if not len(frames) == len(stored[2]) == len(stored[3]) + 1 == len(masks) == len(stored[4]):
+                raise AssertionError(f"{path}, {frames.shape}, {stored[2].shape}, {stored[3].shape}, {masks.shape}")
+            f0, m0 = int(self.frame_offsets[i]), int(self.mask_offsets[i])
+            self.frames[f0:f0 + frames.size].copy_(torch.from_numpy(np.ascontiguousarray(frames).reshape(-1)))
+            self.raw_masks[m0:m0 + masks.size].copy_(torch.from_numpy((masks != 0).astype(np.uint8).reshape(-1)))
+            rows.append(dataset.numerics(pipe, stored, folder, path))
+            self.robots.append(stored[5])
+            self.folders.append(folder)
+        self.lengths_host = self.shapes[:, 0].copy()
+        self.lengths = torch.from_numpy(self.lengths_host.astype(np.int32)).to(self.device)
+        self.tables, self.host_rows = {}, {}
+        for k in rows[0]:
+            first = np.asarray(rows[0][k])
+            if k in WINDOW_TABLES:
+                table = np.zeros((V, Lmax - (k in STEP_TABLES), first.shape[1]), np.float32)
+            elif k in VIDEO_TABLES and first.dtype == np.float32:
+                table = np.zeros((V, first.shape[0]), np.float32)
+            else:  # fp64 camera rows, flags, bounds a file stores as float64: collated from the host, as the loader does
+                self.host_rows[k] = [r[k] for r in rows]
+                continue
+            for i, r in enumerate(rows):
+                a = np.asarray(r[k])
+                if a.dtype != np.float32 or a.shape[1 if k in WINDOW_TABLES else 0:] != table.shape[2 if k in WINDOW_TABLES else 1:]:
+                    raise ValueError(f"{paths[i]}: {k} {a.dtype} {a.shape} next to {first.dtype} {first.shape}")
+                if k in WINDOW_TABLES:
+                    table[i, :len(a)] = a
+                else:
+                    table[i] = a
+            self.tables[k] = torch.from_numpy(table).to(self.device)
+        torch.cuda.synchronize(self.device)
+
+    def __len__(self):
+        return len(self.paths)
+
+    def nbytes(self) -> int:
+        return (self.frames.numel() + self.raw_masks.numel()
+                + sum(t.numel() * t.element_size() for t in self.tables.values()))
+
+    def check(self, index, start):
+        return check_windows(index, start, self.lengths_host, self.window)
+
+    def collate(self, choices):
+        """B `ResidentChoice`s -> the batch dict: one `rac_image_job` per sample pointing at its window inside the
+        store's buffers, `image_shape`, int32 `index` / `start`, the strings, `idx`, and the store itself."""
+        idx = [int(c.idx) for c in choices]
+        index, start = self.check(idx, [int(c.start) for c in choices])
+        p0 = choices[0].params
+        jobs = np.zeros(len(choices), IMAGE_JOB)
+        for job, c, i, s in zip(jobs, choices, index, start):
+            p = c.params
+            if (p.h, p.w) != (p0.h, p0.w):
+                raise ValueError(f"resident batch: model sizes {(p.h, p.w)} and {(p0.h, p0.w)} in one batch")
+            _, Hs, Ws = (int(v) for v in self.shapes[i])
+            job["frame_offset"] = self.frame_offsets[i] + int(s) * Hs * Ws * 3
+            job["mask_offset"] = self.mask_offsets[i] + int(s) * Hs * Ws
+            job["Hs"], job["Ws"] = Hs, Ws
+            job["top"], job["left"], job["th"], job["tw"] = p.top, p.left, p.th, p.tw
+            job["order"], job["factor"], job["jitter"] = p.order, p.factors, int(p.jitter)
+        out = {RESIDENT_KEY: self, "image_jobs": torch.from_numpy(jobs.view(np.uint8).reshape(len(choices), IMAGE_JOB.itemsize)),
+               "image_shape": torch.tensor([self.window, p0.h, p0.w]), "index": torch.from_numpy(index),
+               "start": torch.from_numpy(start), "robot": [self.robots[i] for i in idx],
+               "folder": [self.folders[i] for i in idx], "file_path": [self.paths[i] for i in idx],
+               "idx": torch.tensor(idx, dtype=torch.int64)}
+        for k, per_video in self.host_rows.items():
+            out[k] = data.default_collate([per_video[i] for i in idx])
+        return out
+
+    def gather(self, index, start, L=None):
+        """Time-first windows of every table for int32 DEVICE tensors `index` / `start` the caller has checked
+        (`check`): {states (L, B, R), actions (L - 1, B, A), qpos (L, B, J), low / high (B, 5), ...}, one
+        `rac_window_gather` launch per 8 tables on the current stream."""
+        L = self.window if L is None else int(L)
+        return window_gather([(k, t, k in VIDEO_TABLES, L - (k in STEP_TABLES))
+                              for k, t in self.tables.items()], index, start, self.lengths, L)
+
+    def device_batch(self, batch):
+        """`images`, `masks` and the numeric keys of a collated resident batch, time-first on the store's device, all on
+        the current stream: the job array and the (index, start) pairs are uploaded, `rac_image_pipeline` reads the
+        resident frames and `rac_window_gather` the resident tables.  Also returns the tensors the launches read that
+        the store does not own, for the caller to keep until they have run."""
+        jobs, T, h, w = _image_jobs(batch)
+        index, start = self.check(batch["index"].numpy(), batch["start"].numpy())
+        if T != self.window:
+            raise ValueError(f"resident batch: windows of {T} frames from a store built for {self.window}")
+        host = [_pinned(batch["image_jobs"]), _pinned(torch.from_numpy(np.stack([index, start])))]
+        jobs_dev, pairs = (t.to(self.device, non_blocking=True) for t in host)
+        B = len(jobs)
+        images = torch.empty(T, B, 3, h, w, device=self.device)
+        masks = torch.empty(T, B, 1, h, w, device=self.device)
+        _lib.call("rac_image_pipeline", _lib.ptr(self.frames), _lib.ptr(self.raw_masks), _lib.ptr(jobs_dev),
+                  _lib.ptr(images), _lib.ptr(masks), B, T, h, w, _lib.stream_ptr())
+        out = self.gather(pairs[0], pairs[1], T)
+        out.update(images=images, masks=masks)
+        return out, host + [jobs_dev, pairs]
+
+
+def check_windows(index, start, lengths, window):
+    """The (index, start) pairs of a batch as int32 arrays, refused unless every window of `window` frames lies inside
+    its video of `lengths[index]` frames: `rac_window_gather` and `rac_image_pipeline` read them from device memory,
+    where their entry points cannot look."""
+    index, start, lengths = np.asarray(index), np.asarray(start), np.asarray(lengths)
+    if (index.ndim != 1 or index.shape != start.shape or not len(index)
+            or not (np.issubdtype(index.dtype, np.integer) and np.issubdtype(start.dtype, np.integer))):
+        raise ValueError(f"resident batch: one integer index and start per sample, got {index.shape} and {start.shape}")
+    if index.min() < 0 or index.max() >= len(lengths):
+        raise ValueError(f"resident batch: video index outside [0, {len(lengths)}): {index.tolist()}")
+    if start.min() < 0 or np.any(start + window > lengths[index]):
+        raise ValueError(f"resident batch: a window of {window} from {start.tolist()} leaves its video "
+                         f"(lengths {lengths[index].tolist()})")
+    return index.astype(np.int32), start.astype(np.int32)
+
+
+def window_gather(tables, index, start, lengths, L):
+    """`rac_window_gather` (include/rac_hip.h): for every (name, table, per_video, rows) of `tables` -- fp32 device
+    tensors (V, rows_stored, width), or (V, width) when per_video -- the time-first windows
+    out[name][r][b] = table[index[b]][start[b] + r] as (rows, B, width), or table[index[b]] as (B, width).  `index`,
+    `start` (B,) and `lengths` (V,) are int32 device tensors; the CALLER has checked 0 <= index < V and
+    0 <= start <= length - L (the entry point cannot read them)."""
+    for t in (index, start, lengths):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise _lib.RacError("window_gather: index / start / lengths live on the GPU (no CPU fallback)")
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"window_gather: expected a contiguous int32 vector, got {t.dtype} {tuple(t.shape)}")
+    B, V = int(index.shape[0]), int(lengths.shape[0])
+    if start.shape[0] != B:
+        raise ValueError(f"window_gather: {B} indices and {start.shape[0]} starts")
+    out, records = {}, []
+    for name, t, per_video, rows in tables:
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise _lib.RacError(f"window_gather: table {name!r} lives on the GPU (no CPU fallback)")
+        if (t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != (2 if per_video else 3) or t.shape[0] != V
+                or t.device != index.device):
+            raise ValueError(f"window_gather: table {name!r} must be contiguous fp32 ({V}, ...) on {index.device}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+        width = int(t.shape[-1])
+        dst = torch.empty((B, width) if per_video else (int(rows), B, width), device=t.device)
+        out[name] = dst
+        records.append((t.data_ptr(), dst.data_ptr(), 1 if per_video else int(t.shape[1]), width,
+                        1 if per_video else int(rows), int(bool(per_video))))
+    with torch.cuda.device(index.device):
+        for k in range(0, len(records), _lib.GATHER_MAX_TABLES):
+            part = records[k:k + _lib.GATHER_MAX_TABLES]
+            array = (_lib.GatherTable * len(part))(*part)
+            _lib.call("rac_window_gather", C.cast(array, C.c_void_p), len(part), _lib.ptr(index), _lib.ptr(start),
+                      _lib.ptr(lengths), V, B, int(L), _lib.stream_ptr())
+    return out
+
+
+class ResidentDataset(data.Dataset):
+    """The dataset of a resident loader: an item is what `RoboNetDataset.__getitem__` draws at random for it -- the
+    window start from the dataset's RandomState, the `ImageParams` from its image pipeline, in that order, from the same
+    streams -- and nothing else: no file is opened.  `collate` makes the batch from the choices and the store."""
+
+    def __init__(self, dataset: RoboNetDataset, store: ResidentVideos):
+        self.dataset, self.store = dataset, store
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, idx):
+        start, _ = self.dataset._window(int(self.store.lengths_host[idx]), self.store.paths[idx])
+        return ResidentChoice(int(idx), int(start), self.dataset._images.draw(), self.store)
 
 
 def _start_epoch(loader, epoch: int):
@@ -760,7 +1169,15 @@ def process_batch(data: dict, device) -> dict:
     """Changes tensor idx from batch-first to time-first and moves it to `device` (robonet_dataset.py:434-451).
     A `device_images` batch gets its `images` / `masks` here: from `rac_image_pipeline` on a GPU, from the host pipeline
     on the CPU (the same tensors as with device_images off)."""
-    if "frames" in data:
+    if RESIDENT_KEY in data:  # a --device_resident batch: everything but the strings is made on the store's device
+        store = data[RESIDENT_KEY]
+        if torch.device(device).type != "cuda" or torch.device(device).index not in (None, store.device.index):
+            raise _lib.RacError(f"a --device_resident batch of {store.device} cannot be made on {device} (no CPU fallback)")
+        with torch.cuda.device(store.device):
+            pictures, _ = store.device_batch(data)  # (the current stream orders the small uploads' reuse)
+        for k in RESIDENT_BATCH_KEYS:
+            del data[k]
+    elif "frames" in data:
         if torch.device(device).type == "cuda":
             with torch.cuda.device(device):
                 images, masks, _ = device_images(data, device)  # (the current stream orders the buffers' reuse)
@@ -813,12 +1230,20 @@ class DevicePrefetcher:
         out = dict(batch)
         raw = None
         with torch.cuda.stream(self.stream):
-            if "frames" in out:  # a device_images batch: upload the raw bytes + jobs, one launch makes images / masks
+            made = ()
+            if RESIDENT_KEY in out:  # a resident batch: the jobs and (index, start) go up, two launches make the tensors
+                tensors, raw = out[RESIDENT_KEY].device_batch(out)  # (the store's buffers outlive every launch)
+                for k in RESIDENT_BATCH_KEYS:
+                    del out[k]
+                out.update(tensors)
+                made = tuple(tensors)
+            elif "frames" in out:  # a device_images batch: upload the raw bytes + jobs, one launch makes images / masks
                 out["images"], out["masks"], raw = device_images(out, self.device)
                 for k in RAW_IMAGE_KEYS:
                     del out[k]
+                made = ("images", "masks")
             for k in TRANSPOSE_KEYS:
-                if k in out and not (raw is not None and k in ("images", "masks")):  # (those are time-first already)
+                if k in out and k not in made:  # (those are time-first already)
                     t = out[k]
                     t = t if t.is_pinned() else t.pin_memory()
                     out[k] = t.to(self.device, non_blocking=True).transpose(0, 1).contiguous()
@@ -855,8 +1280,8 @@ class DevicePrefetcher:
             raise item
         batch, ev = item
         torch.cuda.current_stream(self.device).wait_event(ev)
-        for k in TRANSPOSE_KEYS:
-            if k in batch:
+        for k in TRANSPOSE_KEYS + VIDEO_TABLES:
+            if k in batch and torch.is_tensor(batch[k]) and batch[k].is_cuda:
                 batch[k].record_stream(torch.cuda.current_stream(self.device))
         return batch
 

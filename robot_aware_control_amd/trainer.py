@@ -936,10 +936,10 @@ class PredictionTrainer(object):
         return info
 
     def train_copy_baseline(self, train_loader=None, test_loader=None, transfer_loader=None):
-        """Metrics of the copy baseline over the train and test sets (trainer.py:794-827), and over a transfer loader if
-        the caller hands one in (the reference walks one for `--experiment train_sawyer_multiview` only).  Nothing is
-        trained or saved.  With --wandb every set is logged at steps 0 and 500000 (a horizontal line next to the trained
-        models' curves).  Returns the metrics."""
+        """Metrics of the copy baseline over the train and test sets (trainer.py:794-827), and over a transfer loader: the
+        one the caller hands in, else the experiment's own for `--experiment train_sawyer_multiview` (the only one the
+        reference walks here).  Nothing is trained or saved.  With --wandb every set is logged at steps 0 and 500000 (a
+        horizontal line next to the trained models' curves).  Returns the metrics."""
         cf = self._config
         self._step = 0  # (trainer.py:798 loads a checkpoint's step; a model without parameters has none)
         if train_loader is None and test_loader is None:
@@ -947,7 +947,11 @@ class PredictionTrainer(object):
                 _, test_loader = self._setup_data()  # (the synthetic training stream has no end: the test set only)
             else:
                 from . import data as D
-                train_loader, test_loader = D.create_loaders(cf)  # (the loaders themselves: no device prefetch thread)
+                # (the loaders themselves: no device prefetch thread.  The reference walks a transfer set of its own for
+                # train_sawyer_multiview only, trainer.py:818-825)
+                walk_transfer = cf.experiment == "train_sawyer_multiview" and transfer_loader is None
+                train_loader, test_loader, own_transfer = D.experiment_loaders(cf, transfer=walk_transfer)
+                transfer_loader = own_transfer if walk_transfer else transfer_loader
         info = {}
         self.eval_history = []
         for loader, name, training in ((train_loader, "train", True), (test_loader, "test", False),
@@ -966,7 +970,8 @@ class PredictionTrainer(object):
     def _setup_data(self):
         """(infinite time-first batch generator, test loader).  `--data_root synthetic` feeds the deterministic
         generator of robot_aware_control_amd.synthetic; anything else goes through this package's RoboNet data path
-        (data.py: same files, split and preprocessing as robonet_dataloaders.py:21-80, device prefetch)."""
+        (data.py: the files, split and preprocessing of the experiment's own loaders in the reference, device
+        prefetch)."""
         cf = self._config
         from . import data as D
         rank = dist.get_rank() if _dist_on() else 0
@@ -985,9 +990,11 @@ class PredictionTrainer(object):
                                         cf.image_height, cf.image_width, cf.robot_dim, cf.action_dim, seed=cf.seed + 7),
                 batch_size=getattr(cf, "test_batch_size", cf.batch_size))
             return gen(), test
-        train_loader, test_loader = D.create_loaders(cf)
-        if cf.experiment == "train_robonet":  # zero-shot performance on the unseen locobot (trainer.py:899-913)
-            self.transfer_loader = D.create_transfer_loader(cf)
+        # each --experiment's own split (trainer.py:899-947); a transfer loader measures zero-shot performance: on the
+        # unseen locobot for train_robonet, on the unseen sawyer viewpoint for train_sawyer_multiview
+        train_loader, test_loader, transfer_loader = D.experiment_loaders(cf)
+        if transfer_loader is not None:
+            self.transfer_loader = transfer_loader
         return D.get_batch(train_loader, self._device), test_loader
 
     def _save_checkpoint(self):

@@ -10,8 +10,13 @@ on; 64x85 -> 48x64 and 64x64 -> 64x64), and loader-fed training: `PredictionTrai
 device prefetcher with `--img_augmentation True`, `--data_threads` 2 and 5, `device_images` off and on alternated over
 three rounds in one process; every timed window ends in a synchronise.  The last line is one JSON record.
 
+`--resident`: the same rounds also time `--device_resident True` (data.ResidentVideos: the split on the device, built
+once outside the timed windows) -- training fed by it, the feed alone in batches/s (prefetcher drained, nothing
+trained) -- and training on one batch that already lies on the device (no data path at all: the ceiling of any feed).
+The record is also written to `--out` (profiles/resident_bench.json).
+
     python tools/bench_data_path.py --cpu-only
-    python tools/bench_data_path.py [--root DIR] [--rounds 3] [--batches 12] [--threads 2,5]
+    python tools/bench_data_path.py [--root DIR] [--rounds 3] [--batches 12] [--threads 2,5] [--resident]
 """
 import argparse
 import json
@@ -116,9 +121,10 @@ def kernel_half(dev, launches=50):
     return out
 
 
-def train_half(root, dev, threads, rounds, batches, warmup):
+def train_half(root, dev, threads, rounds, batches, warmup, resident=False):
     """Loader-fed `_train_video` frames/s: per (data_threads, device_images) a fresh loader + prefetcher per window,
-    `warmup` batches untimed, `batches` timed, a synchronise at both ends."""
+    `warmup` batches untimed, `batches` timed, a synchronise at both ends.  `resident`: every round also has a window
+    fed by the device-resident split, one of that feed alone and one of training on a batch that stays on the device."""
     import bench
     cf = bench.namespace(dev, **vars(data_config(root)))
     from robot_aware_control_amd import synthetic as syn
@@ -127,29 +133,59 @@ def train_half(root, dev, threads, rounds, batches, warmup):
     tr.model.load_state_dict(syn.synth_state_dict(tr.model, seed=11))
     tr.model.train()
     windows = {}
+
+    def window(key, feed, label, train=True):
+        step = tr._train_video if train else (lambda batch: None)
+        for _ in range(warmup):
+            step(next(feed))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(batches):
+            step(next(feed))
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        steps = batches * tr.steps_per_train_video
+        rec = {"loaded_frames_per_s": round(batches * cf.batch_size * T_VIDEO / dt, 1), "ms_per_batch": round(1e3 * dt / batches, 2)}
+        if train:
+            rec["train_frames_per_s"] = round(steps * cf.batch_size * (cf.n_past + cf.n_future) / dt, 1)
+        else:
+            rec["batches_per_s"] = round(batches / dt, 1)
+        windows.setdefault(key, []).append(rec)
+        print(f"train {label}: {rec}", flush=True)
+
+    def prefetched(key, loader, label, train=True):
+        pf = D.DevicePrefetcher(loader, dev)
+        window(key, pf, label, train)
+        pf.close()
+        pf.thread.join(60)
+
+    resident_loader = still = None
+    if resident:
+        cf.data_threads, cf.device_images, cf.device_resident = 0, True, True
+        t0 = time.perf_counter()
+        resident_loader, _ = D.create_loaders(cf)
+        store = resident_loader.dataset.store
+        windows["resident_store"] = {"videos": len(store), "mb": round(store.nbytes() / 2 ** 20, 1),
+                                     "build_s": round(time.perf_counter() - t0, 2)}
+        print(f"resident store: {windows['resident_store']}", flush=True)
+        cf.device_resident = False
+        still = D.process_batch(next(iter(resident_loader)), dev)
     for r in range(rounds):
         for nt in threads:
             for on in (False, True):
                 cf.data_threads, cf.device_images = nt, on
                 train_loader, _ = D.create_loaders(cf)
-                pf = D.DevicePrefetcher(train_loader, dev)
-                for _ in range(warmup):
-                    tr._train_video(next(pf))
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(batches):
-                    tr._train_video(next(pf))
-                torch.cuda.synchronize()
-                dt = time.perf_counter() - t0
-                pf.close()
-                pf.thread.join(60)
-                del pf, train_loader
-                steps = batches * tr.steps_per_train_video
-                rec = {"loaded_frames_per_s": round(batches * cf.batch_size * T_VIDEO / dt, 1),
-                       "train_frames_per_s": round(steps * cf.batch_size * (cf.n_past + cf.n_future) / dt, 1),
-                       "ms_per_batch": round(1e3 * dt / batches, 2)}
-                windows.setdefault(f"threads{nt}_{'device' if on else 'host'}", []).append(rec)
-                print(f"train round {r} data_threads {nt} device_images {on}: {rec}", flush=True)
+                prefetched(f"threads{nt}_{'device' if on else 'host'}", train_loader,
+                           f"round {r} data_threads {nt} device_images {on}")
+                del train_loader
+        if resident:
+            prefetched("resident", resident_loader, f"round {r} device_resident")
+            prefetched("resident_feed_alone", resident_loader, f"round {r} device_resident, feed alone", train=False)
+
+            def same_batch():
+                while True:
+                    yield dict(still)
+            window("device_batch_no_feed", same_batch(), f"round {r} one batch on the device, no feed")
     return windows
 
 
@@ -164,6 +200,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--threads", default="2,5")
     ap.add_argument("--no-train", action="store_true", help="GPU half: the kernel timing only")
+    ap.add_argument("--resident", action="store_true", help="also time the --device_resident feed; writes --out")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resident_bench.json"))
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         root = a.root
@@ -179,7 +217,13 @@ def main():
             result["kernel"] = kernel_half(dev)
             if not a.no_train:
                 result["train"] = train_half(root, dev, [int(t) for t in a.threads.split(",")], a.rounds, a.batches,
-                                             a.warmup)
+                                             a.warmup, a.resident)
+        if a.resident and "train" in result:
+            result["shape"] = {"batch": 16, "video_length": T_VIDEO, "stored": [Hs, Ws], "model": [h, w],
+                               "rounds": a.rounds, "batches": a.batches, "warmup": a.warmup}
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(result, f, indent=1)
         print(json.dumps(result))
 
 
