@@ -643,6 +643,38 @@ int rac_cem_rollout_sheet(const float* frames, int64_t step_stride, int64_t cand
                           int32_t T, const uint8_t* start_u8, const uint8_t* goal_u8, int32_t G, const uint8_t* goal_mask,
                           float* obs, uint8_t* sheet, int32_t H, int32_t W, void* stream);
 
+/* Also added within version 12.  The action-sweep probe's output (src/prediction/test_action_rollout.py:152-174 over
+ * src/utils/plot.py:32-81,109-115) from rollouts that stayed on the device, one launch for both outputs.
+ * Inputs: truth -- frame t of video i is the planar (3, H, W) fp32 image at truth + t*truth_t_stride + i*truth_b_stride
+ * (strides in elements: the caller passes the time-first batch (T, B, 3, H, W) as it is; the first L frames of the first
+ * b videos are read); gen -- fp32 (S, G, L, b, 3, H, W), contiguous: S sweeps, G sample columns, L frames.
+ *   sheets   (NULL or uint8 (S, L, b*H, (1+G)*W + G, 3)): row block i of sheet (s, t) is
+ *            [u8(truth[t][i]) | 255 | u8(gen[s][0][t][i]) | 255 | ... | u8(gen[s][G-1][t][i])], images as (H, W, 3): the
+ *            reference's save_gif layout -- its inner image_tensor call joins a row's images with padding=1 of ones, one
+ *            white pixel column (255, 255, 255) between neighbouring columns; the outer call stacks the row blocks
+ *            with padding=0.  u8(v) is rac_predict_frames' rule: the fp32 product 255.0f * v (no fused multiply-add)
+ *            clamped to [0, 255] and truncated toward zero, NaN -> 0, which is `np.uint8(clamp(v, 0, 1) * 255)`.
+ *   response (NULL or fp32 (S, G, L, b); needs 0 <= base < S, base is ignored without it):
+ *            response[s][g][t][i] = (1 / (3 H W)) sum |gen[s][g][t][i][.] - gen[base][g][t][i][.]|, in fp32.
+ *            Sweep `base` is not compared with itself: its entries are exactly 0, also where a frame holds a NaN.
+ * Reduction order of one response entry (one workgroup of 256 threads = 4 waves of 64 lanes; no atomics, so the number is
+ * bit-reproducible): the image is cut into quads of 4 adjacent pixels of one row, quad q = y*(W/4) + x/4; thread k
+ * takes quads k, k + 256, k + 512, ... in that order and adds, per quad, channel 0's four |d| (pixel x first), then
+ * channel 1's, then channel 2's, each with one fp32 add into its one running sum (every |d| is one fp32 subtraction);
+ * then the xor butterfly inside each wave (lane l adds lane l ^ 32, then ^ 16, 8, 4, 2, 1); then the four wave sums
+ * are added serially, wave 0 first; then one fp32 division by (float)(3 H W).  A value passes through at most
+ * 12*ceil(H*W/1024) + 6 + 3 additions.
+ * W % 4 == 0; truth and gen 16-byte aligned, both strides multiples of 4.  A sheet row is 3*((1+G)*W + G) bytes, no
+ * multiple of 4 for odd G, so neither a row nor a panel starts on a word: a thread looks at the two low address bits of
+ * its own 12 bytes and writes them with naturally aligned stores only -- three words where the bits are 0, otherwise a
+ * byte and / or a halfword up to the word boundary, two words, and the rest as a halfword and / or a byte (`sheets` itself
+ * needs no alignment).  Every output byte and float has exactly one writer and nothing is read back.
+ * S, G, L, b, H < 1, W % 4 != 0, NULL truth / gen, neither output, or a response without a valid base: a non-zero
+ * status, rac_last_error() set, nothing launched. */
+int rac_action_rollout_sheet(const float* truth, int64_t truth_t_stride, int64_t truth_b_stride, const float* gen,
+                             int32_t base, uint8_t* sheets, float* response, int32_t S, int32_t G, int32_t L, int32_t b,
+                             int32_t H, int32_t W, void* stream);
+
 /* Robot-aware CEM inputs for ALL candidates on the device (replaces the per-candidate CPU loop of
  * `robot_model.predict_batch(start_data, thick=True)`, src/cem/trajectory_sampler.py:86-109 over
  * src/dataset/wx250s/wx250s_model.py:121-163 / locobot_model.py:100-140):

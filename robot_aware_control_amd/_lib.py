@@ -186,6 +186,7 @@ _SIGS = {
     "rac_eef_heatmaps": [vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i32, i32, i32, i32, vp],
     "rac_cem_step_tail": [vp, vp, vp, vp, vp, vp, i32, f32, i32, vp, vp, i32, i32, vp],
     "rac_cem_rollout_sheet": [vp, i64, i64, vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp],
+    "rac_action_rollout_sheet": [vp, i64, i64, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "rac_cem_robot_inputs": [vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp, vp, i32, i32, i32, i32, i32, vp],
     "rac_adam_step": [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, vp],
     "rac_adam_frag_multi": [vp, i32, i64, f32, f32, f32, f32, i32, vp],

@@ -1334,4 +1334,142 @@ extern "C" int rac_video_movement(const float* images, int64_t img_video_stride,
   return check_launch("rac_video_movement (score)");
 }
 
+// ---- the action-sweep probe's sheets and response table (test_action_rollout.py, src/utils/plot.py:32-81,109-115) ----
+namespace rac {
+
+constexpr int AS_THREADS = 256;
+
+// the 12 bytes of 4 pixels' (r, g, b) as three little-endian words, nothing blacked
+__device__ __forceinline__ void pack_rgb4(const f32x4 (&c)[3], unsigned (&w)[3]) {
+  unsigned q[12];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) q[j * 3 + ch] = u8_of(c[ch][j], false);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) w[k] = q[4 * k] | (q[4 * k + 1] << 8) | (q[4 * k + 2] << 16) | (q[4 * k + 3] << 24);
+}
+
+// Those 12 bytes to an address whose two low bits are A, with naturally aligned stores only and every byte written
+// once: A == 0 three words; otherwise the 4 - A bytes up to the word boundary (a byte and / or a halfword), two words
+// shifted out of the 96 bits, and the A bytes left over (a halfword and / or a byte).
+template <int A>
+__device__ __forceinline__ void store12(unsigned char* d, const unsigned (&w)[3]) {
+  if (A == 0) {
+    unsigned* o = reinterpret_cast<unsigned*>(d);
+    o[0] = w[0], o[1] = w[1], o[2] = w[2];
+    return;
+  }
+  constexpr int head = (4 - A) & 3;
+  const unsigned long long lo = ((unsigned long long)w[1] << 32) | w[0], hi = ((unsigned long long)w[2] << 32) | w[1];
+  if (head & 1) d[0] = (unsigned char)w[0];
+  if (head & 2) *reinterpret_cast<unsigned short*>(d + (head & 1)) = (unsigned short)(w[0] >> (8 * (head & 1)));
+  unsigned* o = reinterpret_cast<unsigned*>(d + head);
+  o[0] = (unsigned)(lo >> (8 * head));
+  o[1] = (unsigned)(hi >> (8 * head));
+  const unsigned tail = w[2] >> (8 * head);  // bytes 8 + head .. 11
+  unsigned char* t = d + 8 + head;
+  if (A & 2) {
+    *reinterpret_cast<unsigned short*>(t) = (unsigned short)tail;
+    if (A & 1) t[2] = (unsigned char)(tail >> 16);
+  } else {
+    t[0] = (unsigned char)tail;
+  }
+}
+
+// grid S P L b with P = G + 1 - p0 panels (p0 = 1 without sheets: the truth panel has no other use): workgroup
+// (s, p, t, i) owns panel p of row block i of sheet (s, t) -- p == 0 the ground truth, p >= 1 sample g = p - 1 -- and, for
+// p >= 1, response[s][g][t][i].  The image is walked in quads of four adjacent pixels of one row (W % 4 == 0), thread k
+// taking quads k, k + 256, ...: three 16-byte loads, 12 sheet bytes (store12 by the address's own low bits; the owner of
+// a row's last quad also writes the white pixel behind it), and, with a response, three 16-byte loads of the base
+// sweep's frame and 12 adds into the thread's one running sum: channel 0's four |d|, then channel 1's, then channel
+// 2's.  Then the xor butterfly inside each wave (distances 32, 16, ..., 1), the four wave partials added serially, wave
+// 0 first, and one division by (float)(3 H W).  No value crosses a workgroup.
+__global__ void __launch_bounds__(AS_THREADS) action_rollout_sheet_kernel(const float* truth, long truth_t_stride,
+                                                                          long truth_b_stride, const float* gen, int base,
+                                                                          unsigned char* sheets, float* response, int G,
+                                                                          int L, int b, int H, int W, int p0) {
+  __shared__ float sh[AS_THREADS / 64];
+  const int P = G + 1 - p0;
+  int r = blockIdx.x;
+  const int i = r % b;
+  r /= b;
+  const int t = r % L;
+  r /= L;
+  const int p = r % P + p0, s = r / P, g = p - 1;
+  const int HW = H * W, QW = W >> 2, quads = H * QW;
+  const long image = 3L * HW;
+  const float* src;
+  const float* ref = nullptr;
+  if (p == 0) {
+    src = truth + t * truth_t_stride + i * truth_b_stride;
+  } else {
+    src = gen + ((((long)s * G + g) * L + t) * b + i) * image;
+    if (response && s != base) ref = gen + ((((long)base * G + g) * L + t) * b + i) * image;
+  }
+  const long RW = (long)(1 + G) * W + G;  // a sheet row in pixels
+  unsigned char* out = sheets ? sheets + (((((long)s * L + t) * b + i) * H) * RW + (long)p * (W + 1)) * 3 : nullptr;
+  float acc = 0.f;
+  for (int q = threadIdx.x; q < quads; q += AS_THREADS) {
+    const int y = q / QW, x = (q - y * QW) << 2;
+    const int pix = y * W + x;
+    f32x4 v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = *reinterpret_cast<const f32x4*>(src + (long)c * HW + pix);
+    if (ref) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const f32x4 rv = *reinterpret_cast<const f32x4*>(ref + (long)c * HW + pix);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc += fabsf(v[c][j] - rv[j]);
+      }
+    }
+    if (out) {
+      unsigned char* d = out + ((long)y * RW + x) * 3;
+      unsigned w[3];
+      pack_rgb4(v, w);
+      switch (reinterpret_cast<uintptr_t>(d) & 3u) {
+        case 0: store12<0>(d, w); break;
+        case 1: store12<1>(d, w); break;
+        case 2: store12<2>(d, w); break;
+        default: store12<3>(d, w); break;
+      }
+      if (p < G && x == W - 4) d[12] = d[13] = d[14] = 255;  // image_tensor's padding=1 of ones behind this panel
+    }
+  }
+  if (!response || p == 0) return;  // (uniform over the workgroup)
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tot = sh[0];
+#pragma unroll
+    for (int k = 1; k < AS_THREADS / 64; ++k) tot += sh[k];
+    response[(((long)s * G + g) * L + t) * b + i] = tot / (float)(3 * (long)HW);
+  }
+}
+
+}  // namespace rac
+
+extern "C" int rac_action_rollout_sheet(const float* truth, int64_t truth_t_stride, int64_t truth_b_stride,
+                                        const float* gen, int32_t base, uint8_t* sheets, float* response, int32_t S,
+                                        int32_t G, int32_t L, int32_t b, int32_t H, int32_t W, void* stream) {
+  using namespace rac;
+  RAC_REQUIRE(truth && gen && S >= 1 && G >= 1 && L >= 1 && b >= 1 && H >= 1 && W >= 1 && (sheets || response),
+              "rac_action_rollout_sheet: bad args (truth, gen, S, G, L, b, H >= 1 and at least one of sheets / response)");
+  RAC_REQUIRE(W % 4 == 0, "rac_action_rollout_sheet: W %% 4 == 0 (a thread owns 4 pixels of a row)");
+  RAC_REQUIRE(!response || (base >= 0 && base < S), "rac_action_rollout_sheet: response needs 0 <= base < S");
+  RAC_REQUIRE(aligned16(truth) && aligned16(gen) && truth_t_stride % 4 == 0 && truth_b_stride % 4 == 0 &&
+                  truth_t_stride >= 0 && truth_b_stride >= 0 &&
+                  (!response || (reinterpret_cast<uintptr_t>(response) & 3u) == 0),
+              "rac_action_rollout_sheet: 16-byte aligned float buffers, strides multiples of 4");
+  const int p0 = sheets ? 0 : 1;
+  const long blocks = (long)S * (G + 1 - p0) * L * b;
+  RAC_REQUIRE((long)H * W < (1L << 29) && blocks < (1L << 31), "rac_action_rollout_sheet: too many pixels or images");
+  hipLaunchKernelGGL(action_rollout_sheet_kernel, dim3((unsigned)blocks), dim3(AS_THREADS), 0,
+                     reinterpret_cast<hipStream_t>(stream), truth, (long)truth_t_stride, (long)truth_b_stride, gen, base,
+                     sheets, response, G, L, b, H, W, p0);
+  return check_launch("rac_action_rollout_sheet");
+}
+
 RAC_DEVICE_CODE_END

@@ -3204,6 +3204,32 @@ def video_movement(images, masks, time_first: bool = True) -> Tuple[torch.Tensor
     return score, step.t()
 
 
+def action_rollout_sheet(truth, gen, base=None, sheets: bool = True):
+    """The action-sweep probe's sheets and response table in one launch (`rac_action_rollout_sheet`): `truth` the
+    time-first batch (T, B, 3, H, W) or a slice of one along T or B (strides are handed over, nothing is copied while
+    every frame is dense), `gen` (S, G, L, b, 3, H, W) with L <= T and b <= B.  Returns (`sheets`: uint8
+    (S, L, b H, (1 + G) W + G, 3) or None, `response`: fp32 (S, G, L, b), the mean |gen[s] - gen[base]| per frame, or
+    None without a `base`)."""
+    _require_cuda(truth)
+    _require_cuda(gen)
+    if truth.dim() != 5 or gen.dim() != 7:
+        raise _lib.RacError(f"action_rollout_sheet: (T,B,3,H,W) frames and (S,G,L,b,3,H,W) rollouts, got "
+                            f"{tuple(truth.shape)} and {tuple(gen.shape)}")
+    S, G, L, b, Cc, H, W = gen.shape
+    if Cc != 3 or tuple(truth.shape[2:]) != (3, H, W) or truth.shape[0] < L or truth.shape[1] < b:
+        raise _lib.RacError(f"action_rollout_sheet: shapes do not fit (truth {tuple(truth.shape)}, gen {tuple(gen.shape)})")
+    if base is None and not sheets:
+        raise _lib.RacError("action_rollout_sheet: nothing asked for (no sheets, no base)")
+    truth, gen = truth.detach().to(torch.float32), gen.detach().to(torch.float32).contiguous()
+    if not truth[0, 0].is_contiguous():
+        truth = truth.contiguous()
+    out = torch.empty((S, L, b * H, (1 + G) * W + G, 3), device=gen.device, dtype=torch.uint8) if sheets else None
+    response = None if base is None else torch.empty((S, G, L, b), device=gen.device, dtype=torch.float32)
+    call("rac_action_rollout_sheet", ptr(truth), truth.stride(0), truth.stride(1), ptr(gen),
+         -1 if base is None else int(base), ptr(out), ptr(response), S, G, L, b, H, W, stream_ptr())
+    return out, response
+
+
 class ZeroRegion(torch.autograd.Function):
     """zero_robot_region (src/utils/image.py:5-19), out of place."""
 

@@ -122,6 +122,30 @@ class ShardReducer:
             w.wait()
 
 
+def model_step(model, cf, i, x_j, masks, states, ac, heatmaps, skip, *, posterior, force_use_prior=False, dontcare):
+    """One model step of a rollout: frame i's decoder output from the frame `x_j` fed as frame i - 1 and the window's
+    (T, B, ...) `masks`, `states`, `ac` and `heatmaps` (None: no heatmap input).  Returns (x4, the skip maps for the
+    next step, (mu, logvar, mu_p, logvar_p)) -- `--model det` has no latents: None.  The caller picks `x_j`,
+    composites `x4` over it and scores the frame.  (The trainer's rollouts and `action_rollout.rollout` share it.)"""
+    m_j, r_j, a_j = masks[i - 1], states[i - 1], ac[i - 1]
+    if cf.last_frame_skip:
+        skip = None
+    m_in = torch.cat([m_j, masks[i]], 1) if cf.model_use_future_mask else m_j
+    zero_mask = m_j if dontcare else None
+    if cf.model == "det":  # trainer.py:383-384, 628-629: no prior / posterior, no future robot state, no heatmap
+        x4, curr_skip = model.forward_maps(x_j, m_in, r_j, a_j, skip, zero_mask=zero_mask)
+        latents = None
+    else:
+        r_in = (r_j, states[i]) if cf.model_use_future_robot_state else r_j
+        hm_in = None
+        if heatmaps is not None:
+            hm_in = torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap else heatmaps[i - 1]
+        x4, curr_skip, *latents = model.forward_maps(
+            x_j, m_in, r_in, hm_in, a_j, posterior, states[i] if posterior else None, skip,
+            force_use_prior=force_use_prior, zero_mask=zero_mask)
+    return x4, (curr_skip if i <= cf.n_past else skip), latents  # the encoder's skip maps of the context frames only
+
+
 class PredictionTrainer(object):
     """Video prediction training (reference trainer.py:53-897, hot path only)."""
 
@@ -300,28 +324,9 @@ class PredictionTrainer(object):
         return all_losses
 
     def _model_step(self, i, x_j, masks, states, ac, heatmaps, skip, *, posterior, force_use_prior=False, dontcare):
-        """One model step of a rollout: frame i's decoder output from the frame `x_j` fed as frame i - 1 and the window's
-        (T, B, ...) `masks`, `states`, `ac` and `heatmaps` (None: no heatmap input).  Returns (x4, the skip maps for the
-        next step, (mu, logvar, mu_p, logvar_p)) -- `--model det` has no latents: None.  The caller picks `x_j`,
-        composites `x4` over it and scores the frame."""
-        cf = self._config
-        m_j, r_j, a_j = masks[i - 1], states[i - 1], ac[i - 1]
-        if cf.last_frame_skip:
-            skip = None
-        m_in = torch.cat([m_j, masks[i]], 1) if cf.model_use_future_mask else m_j
-        zero_mask = m_j if dontcare else None
-        if cf.model == "det":  # trainer.py:383-384, 628-629: no prior / posterior, no future robot state, no heatmap
-            x4, curr_skip = self.model.forward_maps(x_j, m_in, r_j, a_j, skip, zero_mask=zero_mask)
-            latents = None
-        else:
-            r_in = (r_j, states[i]) if cf.model_use_future_robot_state else r_j
-            hm_in = None
-            if heatmaps is not None:
-                hm_in = torch.cat([heatmaps[i - 1], heatmaps[i]], 1) if cf.model_use_future_heatmap else heatmaps[i - 1]
-            x4, curr_skip, *latents = self.model.forward_maps(
-                x_j, m_in, r_in, hm_in, a_j, posterior, states[i] if posterior else None, skip,
-                force_use_prior=force_use_prior, zero_mask=zero_mask)
-        return x4, (curr_skip if i <= cf.n_past else skip), latents  # the encoder's skip maps of the context frames only
+        """`model_step` of this trainer's model and configuration."""
+        return model_step(self.model, self._config, i, x_j, masks, states, ac, heatmaps, skip, posterior=posterior,
+                          force_use_prior=force_use_prior, dontcare=dontcare)
 
     def _per_robot_losses(self, x_pred, x_i, m_i, robot_name, all_robots):
         """[(robot, its samples' (3,) [loss, robot_mse, world_mse])] of a batch that mixes robots: the per-robot logging
