@@ -844,6 +844,50 @@ int rac_window_gather(const rac_gather_table* tables, int32_t n_tables, const in
 int rac_mask_compare(const float* pred, const float* truth, int32_t* counts, uint8_t* frames, int32_t V, int32_t T,
                      int32_t H, int32_t W, void* stream);
 
+/* Robot masks from joint positions (the reference's MuJoCo mask environments, src/env/robotics/masks/base_mask_env.py:
+ * set the joints, forward kinematics, a segmentation render from one fixed camera, the robot geoms' pixels), P poses in
+ * ONE launch, one workgroup per pose:  qpos[P][J] (row stride qpos_stride) -> masks[P][h][w] fp32, 0 or 1.
+ *   links[L] (DEVICE memory, parents first, link 0 the world with parent -1):  X_link = X_parent local J, where J is
+ *          T(anchor) R(axis, q) T(-anchor) for a hinge, T(axis q) for a slide, the identity without a joint;
+ *          q = qpos[p][qcol], 0 where qcol < 0.  `local` is T(pos) R(quat) as a row-major 3x4, `axis` a unit vector.
+ *   tri    [9][tri_stride] fp32, structure of arrays: coordinate (3 vertex + xyz) major, triangle minor, LINK-LOCAL;
+ *          tri_meta[N] = link | robot << 8.  other_geoms != 0 when some triangle is not robot (a second depth buffer).
+ *   camera cam_local (HOST, 12 floats): the camera's pose in link cam_link, MuJoCo's camera frame (looks along -z, +x
+ *          right, +y up).  f = 0.5 H / tan(fovy / 2), fovy in degrees;  u = W/2 + f x/d, v = H/2 - f y/d with d = -z is
+ *          MuJoCo's image, handed out bottom-up and with its columns reversed as the reference environment does:
+ *          pixel (row r, col c) samples u = W - (c + 0.5), v = H - (r + 0.5).  For a camera posed as
+ *          set_opencv_camera_pose(ext) poses it (R(ext) Ry(180 deg)) that is the OpenCV pinhole image of camera-to-world
+ *          ext: x right, y down, z forward, fx = fy = f, cx = W/2, cy = H/2.
+ *   coverage: a pixel centre is inside a triangle when all three edge functions have the sign of its area or are zero;
+ *          triangles are double-sided, zero-area ones skipped, and a triangle with ANY vertex nearer than 0.01 m along
+ *          the optical axis is dropped whole (no clipping).
+ *   depth: d, interpolated as affine 1/d; a pixel is robot iff its nearest robot hit is not farther than its nearest
+ *          other hit.  Integer atomic min in LDS on the float's bits: the result does not depend on thread order.
+ *   resize: (h, w) == (H, W) writes the render; otherwise an output pixel is set iff a tap with non-zero weight of the
+ *          bilinear resize (align_corners = False, no antialias; weights in fp32, products and sums rounded separately)
+ *          is set.
+ * native: NULL or [P][H][W], the render before the resize.  link_xpos: NULL or [P][L][3], the links' world positions.
+ * EINVAL, nothing launched: H W > RAC_RENDER_MAX_PIXELS (two H W buffers of 4 bytes must fit LDS), L outside
+ * 1..RAC_RENDER_MAX_LINKS, cam_link outside the links, fovy outside (0, 180), a NULL input.  The caller guarantees
+ * parent < own index, qcol < J and tri_meta's link < L; the kernel clamps all three, so a bad table reads nothing outside
+ * the tables. */
+#define RAC_RENDER_MAX_LINKS 64
+#define RAC_RENDER_MAX_PIXELS 16384
+typedef struct rac_render_link {
+  float local[12];
+  float axis[3];
+  float anchor[3];
+  int32_t parent;
+  int32_t joint; /* 0 none, 1 hinge, 2 slide */
+  int32_t qcol;
+  int32_t reserved;
+} rac_render_link;
+int rac_render_link_bytes(void);
+int rac_render_masks(const float* qpos, int64_t qpos_stride, int32_t P, int32_t J, const rac_render_link* links,
+                     int32_t L, const float* tri, int64_t tri_stride, const int32_t* tri_meta, int32_t N,
+                     int32_t other_geoms, const float* cam_local, int32_t cam_link, float fovy, int32_t H, int32_t W,
+                     int32_t h, int32_t w, float* masks, float* native, float* link_xpos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

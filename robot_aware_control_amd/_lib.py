@@ -75,6 +75,13 @@ class HeatmapView(C.Structure):
                 ("reserved", i32)]
 
 
+class RenderLink(C.Structure):
+    """struct rac_render_link (include/rac_hip.h): one link of a rac_render_masks launch."""
+    _fields_ = [("local", f32 * 12), ("axis", f32 * 3), ("anchor", f32 * 3), ("parent", i32), ("joint", i32),
+                ("qcol", i32), ("reserved", i32)]
+
+
+RENDER_MAX_LINKS, RENDER_MAX_PIXELS = 64, 16384  # RAC_RENDER_MAX_LINKS, RAC_RENDER_MAX_PIXELS
 GATHER_MAX_TABLES = 8  # RAC_GATHER_MAX_TABLES
 
 
@@ -203,6 +210,9 @@ _SIGS = {
     "rac_joint_batch": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "rac_window_gather": [vp, i32, vp, vp, vp, i32, i32, i32, vp],
     "rac_mask_compare": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "rac_render_link_bytes": [],
+    "rac_render_masks": [vp, i64, i32, i32, vp, i32, vp, i64, vp, i32, i32, vp, i32, f32, i32, i32, i32, i32,
+                         vp, vp, vp, vp],
     "rac_version": [],
     "rac_device_arch": [],
     "rac_last_error": [],

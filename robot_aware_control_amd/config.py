@@ -116,7 +116,10 @@ _NATIVE = [("ddp_bucket_mb", I, 64), ("cem_shard", B, True),
            ("eval_best_of_three", B, False),
            # --model_use_heatmap: an .npz of camera matrices (heatmaps.CameraTable.save, tools/export_camera_calibration.py);
            # None: the reference checkout's src/utils/camera_calibration.py
-           ("camera_calibration", S, None)]
+           ("camera_calibration", S, None),
+           # --learned_robot_model: render its masks on the device from this MJCF robot description (render.py) with the
+           # named camera posed from the camera calibration; None: the reference checkout's MuJoCo mask environments
+           ("robot_mjcf", S, None), ("robot_mjcf_camera", S, "main_cam")]
 
 
 def _add(parser, table):

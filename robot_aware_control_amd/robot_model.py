@@ -14,10 +14,12 @@ fused optimisers (optim.make_optimizer) step them in one launch, with a state di
 over `list(joint.parameters()) + list(gripper.parameters())` (joint_pos_trainer.py:98-101).
 
 `LearnedRobotModel` has `PredictionTrainer.robot_model`'s contract: `predict_batch(batch) -> (states, masks)` is the
-reference's `_generate_learned_robot_states` (trainer.py:164-257) -- the whole window is rolled out in one launch, the
-predicted joint positions come to the host in one copy, the masks are rendered (MuJoCo, on the CPU: any object with the
-reference mask envs' `generate_masks(list_of_qpos)`), resized to the frames' size as the reference resizes them, and go
-back in one upload.  There is no CPU fallback.
+reference's `_generate_learned_robot_states` (trainer.py:164-257) -- the whole window is rolled out in one launch; with
+renderers that render on the device (render.MjcfMaskRenderer, `--robot_mjcf`) the masks are made from the joint positions
+where they are, one launch per viewpoint, at the frames' size; with host renderers (MuJoCo on the CPU: any object with
+the reference mask envs' `generate_masks(list_of_qpos)`) the predicted joint positions come to the host in one copy, the
+masks are rendered, resized to the frames' size as the reference resizes them, and go back in one upload.  The planner's
+batch (no `folder`, no `masks`) is answered with every row rendered, row 0 too.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -168,13 +170,44 @@ def resize_masks(rendered, height: int, width: int) -> np.ndarray:
     return (t != 0).numpy()
 
 
-def mask_renderer(renderers, config, viewpoint):
-    """`renderers[viewpoint]`, built on first use from the reference's MuJoCo mask envs (trainer.py:183-203,
-    joint_pos_trainer.py:481-500) where those import; shared by LearnedRobotModel and RobotPredictionTrainer.plot."""
+_EXPERIMENT_ROBOT = {"finetune": "baxter", "finetune_baxter": "baxter", "finetune_widowx": "widowx",
+                     "finetune_sawyer_view": "sawyer"}
+
+
+def mjcf_mask_renderer(config, viewpoint, camera_table=None):
+    """An `MjcfMaskRenderer` (render.py: masks rendered on the device) of `--robot_mjcf`, its camera
+    `--robot_mjcf_camera` posed from the calibration `--model_use_heatmap` reads (heatmaps.CameraTable, key
+    `<robot>_<viewpoint>` with the experiment's robot, or `viewpoint` itself).  NotImplementedError when the
+    calibration has no such entry."""
+    from .heatmaps import CameraTable
+    from .render import MjcfMaskRenderer
+    exp = getattr(config, "experiment", None)
+    table = camera_table if camera_table is not None else CameraTable.from_config(config)
+    keys = ([f"{_EXPERIMENT_ROBOT[exp]}_{viewpoint}"] if exp in _EXPERIMENT_ROBOT else []) + [str(viewpoint)]
+    key = next((k for k in keys if k in table.world_to_camera), None)
+    if key is None:
+        raise NotImplementedError(
+            f"no mask renderer for viewpoint {viewpoint!r}: --robot_mjcf {config.robot_mjcf} is set, but the camera "
+            f"calibration (--camera_calibration, heatmaps.CameraTable) has no world_to_camera entry {' or '.join(keys)} "
+            f"(it has {sorted(table.world_to_camera)}); pass renderers={{viewpoint: env}} to LearnedRobotModel, env being "
+            f"any object with generate_masks(list_of_qpos) -> list of (H, W) arrays")
+    camera = getattr(config, "robot_mjcf_camera", None) or "main_cam"
+    env = MjcfMaskRenderer(config.robot_mjcf, camera=camera)
+    env.set_opencv_camera_pose(camera, np.linalg.inv(table.world_to_camera[key]))
+    return env
+
+
+def mask_renderer(renderers, config, viewpoint, camera_table=None):
+    """`renderers[viewpoint]`, built on first use: from `--robot_mjcf` when that is set (mjcf_mask_renderer), else from
+    the reference's MuJoCo mask envs (trainer.py:183-203, joint_pos_trainer.py:481-500) where those import; shared by
+    LearnedRobotModel and RobotPredictionTrainer.plot."""
     env = renderers.get(viewpoint)
     if env is not None:
         return env
     exp = getattr(config, "experiment", None)
+    if getattr(config, "robot_mjcf", None):
+        env = renderers[viewpoint] = mjcf_mask_renderer(config, viewpoint, camera_table)
+        return env
     try:  # the reference's MuJoCo mask envs: only inside a full reference checkout
         from src.utils.camera_calibration import camera_to_world_dict
         if exp in ("finetune", "finetune_baxter"):
@@ -230,16 +263,43 @@ class LearnedRobotModel:
         return ops.robot_rollout(jp, gp, qpos0, state0, actions)
 
     def _renderer(self, viewpoint):
-        return mask_renderer(self.renderers, self._config, viewpoint)
+        return mask_renderer(self.renderers, self._config, viewpoint, self.camera_table)
+
+    def _predict_candidates(self, data):
+        """The planner's form of `predict_batch` (trajectory_sampler.py:86-109): `states` (T+1, N, R), `qpos` (T+1, N, J)
+        with row 0 filled, `actions` (T, N, A) -> (states (T+1, N, R), masks (T+1, N, 1, h, w)) on the device, every
+        row -- row 0 too -- rendered from its joint positions by the one renderer (or `default_viewpoint`'s)."""
+        cf = self._config
+        if len(self.renderers) == 1:
+            env = next(iter(self.renderers.values()))
+        else:
+            vp = getattr(cf, "default_viewpoint", None)
+            if vp is None:
+                raise ValueError("LearnedRobotModel.predict_batch on a planner batch needs one renderer or "
+                                 "config.default_viewpoint to choose one")
+            env = self._renderer(vp)
+        q, s = self.rollout(data["qpos"][0], data["states"][0], data["actions"])
+        rows, N, J = q.shape
+        h, w = int(cf.image_height), int(cf.image_width)
+        if not hasattr(env, "render"):
+            raise NotImplementedError("LearnedRobotModel.predict_batch on a planner batch renders every candidate on the "
+                                      "device: its renderer needs render(qpos) (render.MjcfMaskRenderer)")
+        return s, env.render(q.reshape(rows * N, J), out_hw=(h, w)).view(rows, N, 1, h, w)
 
     @torch.no_grad()
-    def predict_batch(self, batch):
+    def predict_batch(self, batch, thick=False):
         """The reference's `_generate_learned_robot_states` (trainer.py:164-257): (states, masks) shaped like the batch's,
         row 0 the ground truth, rows 1..T the models' rollout from row 0 over the window's actions (`raw_actions` when
         `preprocess_action != "raw"`) and the render of every predicted joint position from its sample's viewpoint.
         With `model_use_heatmap` a third tensor: the batch's `heatmaps` with rows 1..T rebuilt from the predicted states
-        (trainer.py:234-256), each sample with its own `low` / `high` / `robot` / `folder`, in one launch."""
+        (trainer.py:234-256), each sample with its own `low` / `high` / `robot` / `folder`, in one launch.
+        Renderers with `render` (render.MjcfMaskRenderer) take the device route: one launch per distinct viewpoint on
+        the predicted joint positions where they are, written into the masks -- no copy to the host and none back.
+        A batch without `folder` and `masks` is the planner's (`_predict_candidates`); `thick` is the analytical models'
+        argument and changes nothing here (the reference's wx250s environment always renders every geom)."""
         cf = self._config
+        if "folder" not in batch and "masks" not in batch:
+            return self._predict_candidates(batch)
         use_heatmap = bool(getattr(cf, "model_use_heatmap", False))
         if use_heatmap and "heatmaps" not in batch:
             raise NotImplementedError("model_use_heatmap with the learned robot model: the batch carries no `heatmaps` "
@@ -256,7 +316,20 @@ class LearnedRobotModel:
         pred_states[:T + 1] = s
         pred_masks = torch.zeros(tuple(mask.shape), device=dev, dtype=mask.dtype)
         pred_masks[0] = torch.as_tensor(mask[0]).to(dev)
-        if T:
+        if T and all(hasattr(env, "render") for env in envs.values()):
+            h, w = int(cf.image_height), int(cf.image_width)
+            if (h, w) != tuple(mask.shape[-2:]):
+                raise ValueError(f"image_height x image_width is {h} x {w}, the batch's masks are {tuple(mask.shape[-2:])}")
+            J = q.shape[-1]
+            for vp, env in envs.items():
+                cols = [b for b, f in enumerate(folders) if f == vp]
+                if len(cols) == B and pred_masks.dtype == torch.float32 and tuple(mask.shape[2:]) == (1, h, w):
+                    env.render(q[1:].reshape(T * B, J), out_hw=(h, w), out=pred_masks[1:T + 1].view(T * B, 1, h, w))
+                else:
+                    idx = torch.tensor(cols, device=dev)
+                    rendered = env.render(q[1:].index_select(1, idx).reshape(T * len(cols), J), out_hw=(h, w))
+                    pred_masks[1:T + 1, idx] = rendered.view((T, len(cols)) + tuple(mask.shape[2:])).to(mask.dtype)
+        elif T:
             q_host = q[1:].cpu().numpy()  # the one device-to-host copy of the window
             h, w = int(cf.image_height), int(cf.image_width)
             if (h, w) != tuple(mask.shape[-2:]):
