@@ -75,7 +75,9 @@ typedef struct rac_conv_args {
   const float* shift;
   double* stats;      /* [G][2][N] fp64 sum / sum of squares of the raw conv output (train BatchNorm), or NULL */
   int64_t stats_rows; /* rows (pixels) per statistics group: G = B*H*W / stats_rows groups (time steps batched along
-                         the batch axis keep per-step statistics); 0 = one group.  Multiple of 128. */
+                         the batch axis keep per-step statistics); 0 = one group.  Multiple of 128.
+                         rac_conv2d_fwd_split on maps it covers with 2-D tiles (3x3, W >= 64): a multiple of 8 W (a tile
+                         is 8 image rows x 16 pixels and counts for the group of its first pixel); refused otherwise. */
   int32_t a0_up;      /* rac_conv2d_fwd_split, maps larger than a 128-pixel tile: a0 is the [B][H/2][W/2][.] tensor whose
                          nearest-neighbour 2x upsampling is the conv's first source (vgg_64.py:205-216, nn.UpsamplingNearest2d
                          before upc3 / upc4 / upc5): pixel (y, x) reads a0 at (y / 2, x / 2); the upsampled tensor is never

@@ -2902,6 +2902,10 @@ static int conv16_launch(const rac_conv_args* a, const uint32_t* a_amax0, const 
     }
     p.tile_m = tile2d ? 128 : rows_tile_m(a->H, a->W);
     RAC_REQUIRE(p.stats_rows % p.tile_m == 0, "rac_conv2d_fwd_split: stats_rows must be a multiple of the tile rows");
+    // (a 2-D tile's 128 pixels are 8 image rows x 16 columns, not 128 consecutive pixels: the statistics group of a tile
+    // is the group of its first pixel, so a group must hold whole bands of 8 image rows)
+    RAC_REQUIRE(!tile2d || p.stats_rows % (8 * a->W) == 0,
+                "rac_conv2d_fwd_split: with 2-D tiles stats_rows must be a multiple of 8 image rows");
     const int nrows = tile2d ? 10 * 18 : p.tile_m + 2 * p.pad * a->W;
     const int nv = cdiv(nrows * 4, 256) < 2 ? 2 : cdiv(nrows * 4, 256);
     RAC_REQUIRE(nv <= 4, "rac_conv2d_fwd_split: halo too large for the LDS image");
