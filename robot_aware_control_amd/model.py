@@ -451,7 +451,8 @@ class _FlatModel(nn.Module):
         gate = ops.PARAM_GATE  # an optimiser update still in flight: optim.ShardedAdam's all-gather, FusedAdam's late groups
         if gate is not None and getattr(gate, "_model", self) is not self:
             gate.wait_params()  # another model's optimiser (a previous trainer of this process): let it land and drop it
-            gate = ops.PARAM_GATE = None
+            ops.release_gate(gate)
+            gate = None
         if gate is not None:
             gate.wait_params(upto=self._encoder_extent())
         out = self._encode_now(image, mask, heatmap, zero_mask, n_updates, groups)

@@ -17,6 +17,7 @@ weights.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 import functools
@@ -88,7 +89,23 @@ def _cdiv(a, b):
 # Convs whose input-channel count is not a multiple of 4 (first encoder layer: 3..7 channels; the three input
 # convs: g + 5..15 (+ z)) run on a zero-padded copy of the weight ([Cout][k][k][Cpad], 16-byte rows) so that they
 # take the vector-load kernel; their inputs are produced already padded (rac_pack_input / rac_tilecat_fwd `pad`).
-PARAM_EPOCH = 0  # bumped by FusedAdam.step(): parameters changed behind torch's version counters
+PARAM_EPOCH = 0  # bumped by the optimisers' steps (params_changed): parameters changed behind torch's version counters
+
+
+def params_changed() -> None:
+    """An optimiser wrote the parameters through the flat buffer: whatever is cached from them (padded weight copies,
+    operand parts) and not marked current again by the writer (_WeightStore.mark_current) is stale."""
+    global PARAM_EPOCH
+    PARAM_EPOCH += 1
+
+
+def _version_tag(t: torch.Tensor, follow_sources: bool = False):
+    """What a cached derivative of `t` is valid for: torch's version counter, PARAM_EPOCH, the address.  `follow_sources`:
+    a view over several parameters (`_rac_sources`: the merged mu | logvar head) changes when any of them does -- an
+    in-place update bumps ITS parameter's counter, not the view's."""
+    src = getattr(t, "_rac_sources", None) if follow_sources else None
+    ver = t._version if src is None else tuple(s._version for s in src)
+    return (ver, PARAM_EPOCH, t.data_ptr())
 
 
 def pad4(c: int) -> int:
@@ -98,7 +115,7 @@ def pad4(c: int) -> int:
 def _derived(weight: torch.Tensor, slot: str, build):
     """Cache a tensor derived from a parameter ON the parameter object (dies with it; a data_ptr key could be
     re-used by the allocator), invalidated by in-place updates (torch version counter or PARAM_EPOCH)."""
-    tag = (weight._version, PARAM_EPOCH, weight.data_ptr())
+    tag = _version_tag(weight)
     hit = getattr(weight, slot, None)
     if hit is not None and hit[0] == tag:
         return hit[1]
@@ -121,7 +138,7 @@ def padded_weight(weight: torch.Tensor, cp: Optional[int] = None) -> torch.Tenso
             setattr(weight, f"_rac_padbuf{cp}", wp)
             wp._rac_pad_source = (weakref.ref(weight), cp)
         call("rac_pad_rows", ptr(weight_mem(weight)), ci, ptr(wp), cp, co * k * k, stream_ptr())
-        ent = _WP_ENTRIES.get(id(wp))
+        ent = weight_entry(wp)
         if ent is not None:  # rewritten behind torch's version counter: its cached operand parts are stale
             ent.tag = None
         return wp
@@ -460,49 +477,57 @@ def split_supported(H: int, W: int, k: int, Cin: int, Cout: int, a_split: int = 
     return ok
 
 
-# Split-precision weight operands.  Every conv weight that runs on the fp16 pipe is registered here with its amax slot
-# and its fragment-order parts (forward and / or transposed); after an optimiser step ALL of them are stale at once and
-# are refreshed by three launches (zero the slots, rac_absmax_multi, rac_weight_frag_split_multi) instead of three per
-# weight and direction.  A weight that goes stale on its own (a new registration) takes the single-tensor calls.
+# Split-precision weight operands.  Every conv weight that runs on the fp16 pipe is registered in its device's
+# _WeightStore with its amax slot and its fragment-order parts (forward and / or transposed); after an optimiser step ALL
+# of them are stale at once and are refreshed by three launches (zero the slots, rac_absmax_multi,
+# rac_weight_frag_split_multi) instead of three per weight and direction.  A weight that goes stale on its own (a new
+# registration) takes the single-tensor calls.
 class _WeightParts:
-    # slot: what the convs read as the weight's maximum (exact after a refresh here; an upper bound after a fused
-    # optimiser step, fused_adam_step); exact_ok: the device's `exact` array holds the exact maximum of the CURRENT values
-    __slots__ = ("ref", "idx", "slot", "device", "parts", "tag", "exact_ok", "__weakref__")
+    """One registered weight (`ref`: a weak reference).  `slot` is what the convs read as its maximum -- exact after a
+    refresh, an upper bound after fused_adam_step -- and `exact` the cell that holds the exact maximum of the CURRENT values
+    while `exact_ok`: cell `idx` of the store's two arrays.  `parts`: {transposed: fp16 fragment parts}; `tag`: the version
+    of the weight that parts and slot were written for (None: never, or rewritten behind the counters)."""
+    __slots__ = ("ref", "idx", "slot", "exact", "parts", "tag", "exact_ok", "_sig")
+
+    def __init__(self, store, idx):
+        self.idx, self.slot, self.exact = idx, store.slots[idx:idx + 1], store.exact[idx:idx + 1]
+        self.ref, self.parts, self.tag, self.exact_ok, self._sig = None, {}, None, False, None
+
+    def current(self, w) -> bool:
+        """Do the parts and the slot describe the weight's values as they are now?"""
+        return self.tag == _version_tag(w, True)
+
+    def stamp(self, w) -> None:
+        """... they do: whoever wrote them says so."""
+        self.tag = _version_tag(w, True)
+
+    def add_parts(self, w, transposed: bool):
+        parts = torch.empty((2, w.numel()), device=w.device, dtype=torch.float16)
+        parts._rac_transposed = transposed
+        self.parts[transposed] = parts
+        self.tag = self._sig = None
+
+    def signature(self):
+        """Which parts, where: job tables hold their addresses and are looked up by this."""
+        if self._sig is None:
+            self._sig = tuple(sorted((t, q.data_ptr()) for t, q in self.parts.items()))
+        return self._sig
+
+    def in_flight(self) -> bool:
+        """Is an optimiser update of the parameter memory this weight aliases (a zero-padded copy: its source's) still
+        travelling (PARAM_GATE)?  Nothing may read it yet."""
+        gate, w = PARAM_GATE, self.ref()
+        if gate is None or w is None:
+            return False
+        src = getattr(w, "_rac_pad_source", None)
+        base = w if src is None else src[0]()
+        return base is not None and not gate.ready(base)
 
 
-_WP_ENTRIES = {}  # id(weight) -> _WeightParts
-_WP_DEV = {}      # device -> {"slots", "free", "sig", "tables"}
-_WP_NSLOTS = 1024
+_STORE_SLOTS = 1024
 
 
-def _wp_state(device):
-    st = _WP_DEV.get(device)
-    if st is None:
-        st = _WP_DEV[device] = {"slots": torch.zeros(_WP_NSLOTS, device=device, dtype=torch.int32),
-                                "exact": torch.zeros(_WP_NSLOTS, device=device, dtype=torch.int32),
-                                "free": list(range(_WP_NSLOTS - 1, -1, -1)), "tables": {}, "adam_plan": None,
-                                "optim_plan": None}
-    return st
-
-
-def _wp_drop(key, device, idx, _ref):
-    ent = _WP_ENTRIES.get(key)
-    if ent is not None and ent.idx == idx and ent.device == device:
-        del _WP_ENTRIES[key]
-        st = _WP_DEV.get(device)
-        if st is not None:
-            st["free"].append(idx)
-
-
-def _wp_tag(weight):
-    # a view over several parameters (the merged mu | logvar head) changes when any of them does: in-place updates of
-    # a parameter bump ITS version counter, not the view's
-    src = getattr(weight, "_rac_sources", None)
-    ver = weight._version if src is None else tuple(t._version for t in src)
-    return (ver, PARAM_EPOCH, weight.data_ptr())
-
-
-def _wp_upload(jobs, device):
+def _upload_jobs(jobs, device):
     raw = bytes(jobs)
     return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
 
@@ -514,8 +539,16 @@ ADAM_WGS = int(os.environ.get("RAC_ADAM_WGS", "0"))  # (experiments: the one-str
 
 # optim.ShardedAdam while the all-gather of the updated parameters is in flight (or optim.FusedAdam while its late weights'
 # update runs on the side stream): `ready(param)` says whether a parameter's
-# buckets have been waited for (its new values may be read by kernels enqueued now).  _wp_refresh leaves the others stale.
+# buckets have been waited for (its new values may be read by kernels enqueued now).  _WeightStore.refresh leaves the
+# others stale.  The optimiser installs itself (`ops.PARAM_GATE = self`) and takes itself out with release_gate(self).
 PARAM_GATE = None
+
+
+def release_gate(owner) -> None:
+    """`owner`'s update has been waited for: take it out of PARAM_GATE, unless another optimiser holds the gate by now."""
+    global PARAM_GATE
+    if PARAM_GATE is owner:
+        PARAM_GATE = None
 
 
 def param_wait(t: torch.Tensor = None) -> None:
@@ -532,81 +565,219 @@ def param_wait(t: torch.Tensor = None) -> None:
         gate.wait_params()
 
 
-def _wp_tables(st, items, device):
-    """Job tables (device memory, cached per set of weights) of rac_absmax_multi / rac_weight_frag_split_multi over
-    `items` = [(entry, weight)]: (absmax jobs, n, blocks, fragment jobs, n, blocks, the entries' slot indices)."""
-    lib = _lib.load()
-    sig = tuple((w.data_ptr(), ent.idx, tuple(sorted((t, q.data_ptr()) for t, q in ent.parts.items())))
-                for ent, w in items)
-    tables = st["tables"].get(sig)
-    if tables is None:  # job tables (device memory) for this set of weights
-        if len(st["tables"]) > 8:
-            st["tables"].clear()
-        ajobs = (AbsmaxJob * len(items))()
-        nfrag = sum(len(ent.parts) for ent, _ in items)
-        fjobs = (FragJob * nfrag)()
-        ab = fb = j = 0
-        for i, (ent, w) in enumerate(items):
-            wm = weight_mem(w.detach())
-            co, ci, k, _ = w.shape
-            ajobs[i] = AbsmaxJob(x=ptr(wm), n=wm.numel(), amax=ptr(ent.slot), block_begin=ab)
-            ab += lib.rac_absmax_blocks(wm.numel())
-            for transposed, parts in sorted(ent.parts.items()):
-                fjobs[j] = FragJob(w=ptr(wm), w_amax=ptr(ent.slot), parts=ptr(parts), part_stride=wm.numel(), Cout=co,
-                                   Cin=ci, ksize=k, transposed=1 if transposed else 0, block_begin=fb)
-                fb += lib.rac_weight_frag_blocks(co, ci, k)
-                j += 1
-        idx = torch.tensor([ent.idx for ent, _ in items], device=device, dtype=torch.long)
-        tables = st["tables"][sig] = (_wp_upload(ajobs, device), len(items), ab, _wp_upload(fjobs, device), nfrag, fb, idx)
-    return tables
+class _WeightStore:
+    """The registered weights of ONE device (`_store(device)`) and what the optimiser steps cache about them.
 
+    * `slots` / `exact`: the arena of _STORE_SLOTS maxima.  An entry owns cell `idx` of both from its registration until
+      its weight dies; the weak reference's callback hands the cell back to `free`.
+    * `entries`: id(weight) -> _WeightParts, in registration order, this device's only (a weight stays on the device it
+      was registered on).
+    * `entry.current(w)`: parts and `slot` describe w's values now; `entry.exact_ok`: `exact` does too.  A fused optimiser
+      step needs both of every weight it covers (`covered`), and says so itself afterwards (`mark_current`); everything
+      else goes stale with params_changed() and is caught up by `refresh()` when a conv next asks (weight_parts).
+    * refresh() reads no weight whose memory an optimiser update in flight still owns (PARAM_GATE).
+    * Job tables and optimiser plans hold ADDRESSES (weights, parts, cells, flat buffers).  They are found again by a
+      signature of those addresses and never patched: another signature is another table."""
 
-def _wp_refresh(device):
-    """Bring every registered weight of `device` whose parameter changed up to date."""
-    st = _wp_state(device)
-    stale, n_live = [], 0
-    gate = PARAM_GATE
-    for ent in list(_WP_ENTRIES.values()):
-        if ent.device != device:
-            continue
-        w = ent.ref()
-        if w is None:
-            continue
-        src = getattr(w, "_rac_pad_source", None)
-        if gate is not None:  # (a padded copy, a merged head view: judged by the parameter memory they alias)
-            base = src[0]() if src is not None else w
-            if base is not None and not gate.ready(base):
+    def __init__(self, device):
+        self.device = device
+        self.slots = torch.zeros(_STORE_SLOTS, device=device, dtype=torch.int32)
+        self.exact = torch.zeros(_STORE_SLOTS, device=device, dtype=torch.int32)
+        self.free = list(range(_STORE_SLOTS - 1, -1, -1))
+        self.entries = {}
+        self._tables = {}  # signature of a set of weights -> its job tables
+        self._plans = {}   # "adam" | "optim" -> (signature, the step's plan; None: a layout its tables do not describe)
+
+    def register(self, weight) -> _WeightParts:
+        if not self.free:
+            raise _lib.RacError("too many conv weights registered for the split-precision pipe")
+        co, ci, _, _ = weight.shape
+        if co % 32 or ci % 32:
+            raise _lib.RacError(f"split-precision weight {tuple(weight.shape)}: channel counts must be multiples of 32")
+        key = id(weight)
+        ent = self.entries[key] = _WeightParts(self, self.free.pop())
+        ent.ref = weakref.ref(weight, functools.partial(self._drop, key, ent.idx))
+        return ent
+
+    def _drop(self, key, idx, _ref):
+        """The weight died: its cell is free again."""
+        ent = self.entries.get(key)
+        if ent is not None and ent.idx == idx:
+            del self.entries[key]
+            self.free.append(idx)
+
+    def live(self):
+        """(entry, weight) of the weights that are still alive, in registration order."""
+        for ent in list(self.entries.values()):  # (a copy: a collection under way may drop entries)
+            w = ent.ref()
+            if w is not None:
+                yield ent, w
+
+    def tables(self, items):
+        """Job tables (device memory, cached per set of weights) of rac_absmax_multi / rac_weight_frag_split_multi over
+        `items` = [(entry, weight)]: (absmax jobs, n, blocks, fragment jobs, n, blocks, the entries' slot indices)."""
+        sig = tuple((w.data_ptr(), ent.idx, ent.signature()) for ent, w in items)
+        tables = self._tables.get(sig)
+        if tables is None:
+            if len(self._tables) > 8:
+                self._tables.clear()
+            lib = _lib.load()
+            ajobs = (AbsmaxJob * len(items))()
+            nfrag = sum(len(ent.parts) for ent, _ in items)
+            fjobs = (FragJob * nfrag)()
+            ab = fb = j = 0
+            for i, (ent, w) in enumerate(items):
+                wm = weight_mem(w.detach())
+                co, ci, k, _ = w.shape
+                ajobs[i] = AbsmaxJob(x=ptr(wm), n=wm.numel(), amax=ptr(ent.slot), block_begin=ab)
+                ab += lib.rac_absmax_blocks(wm.numel())
+                for transposed, parts in sorted(ent.parts.items()):
+                    fjobs[j] = FragJob(w=ptr(wm), w_amax=ptr(ent.slot), parts=ptr(parts), part_stride=wm.numel(), Cout=co,
+                                       Cin=ci, ksize=k, transposed=1 if transposed else 0, block_begin=fb)
+                    fb += lib.rac_weight_frag_blocks(co, ci, k)
+                    j += 1
+            idx = torch.tensor([ent.idx for ent, _ in items], device=self.device, dtype=torch.long)
+            tables = self._tables[sig] = (_upload_jobs(ajobs, self.device), len(items), ab,
+                                          _upload_jobs(fjobs, self.device), nfrag, fb, idx)
+        return tables
+
+    def refresh(self) -> None:
+        """Bring every registered weight whose parameter changed up to date."""
+        stale = []
+        gated = PARAM_GATE is not None
+        for ent, w in self.live():
+            if gated and ent.in_flight():  # (a padded copy, a merged head view: judged by the parameter memory they alias)
                 continue
-        if src is not None:  # a zero-padded copy of a parameter: rebuild the copy first
-            param = src[0]()
-            if param is None:
-                continue
-            padded_weight(param, src[1])
-        n_live += 1
-        if ent.tag != _wp_tag(w):
-            stale.append((ent, w))
-    if not stale:
-        return
-    sp = stream_ptr()
-    if len(stale) <= 2:  # a new registration: the single-tensor calls
+            src = getattr(w, "_rac_pad_source", None)
+            if src is not None:  # a zero-padded copy of a parameter: rebuild the copy first
+                param = src[0]()
+                if param is None:
+                    continue
+                padded_weight(param, src[1])
+            if not ent.current(w):
+                stale.append((ent, w))
+        if not stale:
+            return
+        sp = stream_ptr()
+        if len(stale) <= 2:  # a new registration: the single-tensor calls
+            for ent, w in stale:
+                ent.slot.zero_()
+                wm = weight_mem(w.detach())
+                co, ci, k, _ = w.shape
+                call("rac_absmax", ptr(wm), wm.numel(), None, 0, ptr(ent.slot), sp)
+                for transposed, parts in ent.parts.items():
+                    call("rac_weight_frag_split", ptr(wm), ptr(ent.slot), ptr(parts), co, ci, k, 1 if transposed else 0,
+                         wm.numel(), sp)
+                ent.exact.copy_(ent.slot)
+                ent.stamp(w)
+                ent.exact_ok = True
+            return
+        ta, na, ab, tf, nf, fb, idx = self.tables(stale)
+        self.slots.index_fill_(0, idx, 0)  # the stale slots are recomputed (the others may hold bounds of a fused step)
+        call("rac_absmax_multi", ptr(ta), na, ab, sp)
+        call("rac_weight_frag_split_multi", ptr(tf), nf, fb, sp)
+        self.exact.index_copy_(0, idx, self.slots.index_select(0, idx))
         for ent, w in stale:
-            ent.slot.zero_()
-            wm = weight_mem(w.detach())
+            ent.stamp(w)
+            ent.exact_ok = True
+
+    def covered(self, flat):
+        """[(first flat element, entry, weight)] of the registered weights that live in the flat parameter buffer (16-byte
+        aligned, [Cout][k][k][Cin] memory; not the zero-padded copies), in flat order -- None as soon as one of them has
+        parts or a maximum that are not current (first steps, new registrations): a fused optimiser step must wait."""
+        base, nbytes = flat.data_ptr(), flat.numel() * 4
+        covered = []
+        for ent, w in self.live():
+            if getattr(w, "_rac_pad_source", None) is not None:
+                continue
+            off = w.data_ptr() - base
             co, ci, k, _ = w.shape
-            call("rac_absmax", ptr(wm), wm.numel(), None, 0, ptr(ent.slot), sp)
-            for transposed, parts in ent.parts.items():
-                call("rac_weight_frag_split", ptr(wm), ptr(ent.slot), ptr(parts), co, ci, k, 1 if transposed else 0,
-                     wm.numel(), sp)
-            st["exact"][ent.idx:ent.idx + 1].copy_(ent.slot)
-            ent.tag, ent.exact_ok = _wp_tag(w), True
-        return
-    ta, na, ab, tf, nf, fb, idx = _wp_tables(st, stale, device)
-    st["slots"].index_fill_(0, idx, 0)  # the stale slots are recomputed (the others may hold bounds of a fused step)
-    call("rac_absmax_multi", ptr(ta), na, ab, sp)
-    call("rac_weight_frag_split_multi", ptr(tf), nf, fb, sp)
-    st["exact"].index_copy_(0, idx, st["slots"].index_select(0, idx))
-    for ent, w in stale:
-        ent.tag, ent.exact_ok = _wp_tag(w), True
+            if not (0 <= off < nbytes and off % 16 == 0 and w.stride() == (k * k * ci, 1, k * ci, ci)):
+                continue
+            if not (ent.current(w) and ent.exact_ok):
+                return None
+            covered.append((off // 4, ent, w))
+        covered.sort(key=lambda c: c[0])
+        return covered
+
+    def plan(self, kind: str, buffers, covered, build):
+        """The fused step's cached plan for these buffers and covered weights, built by `build()` when either changed.
+        None -- a layout the step's tables do not describe (_flat_layout) -- is remembered in the same way: the step
+        declines again without another walk."""
+        sig = (buffers, tuple((off, ent.idx, ent.signature()) for off, ent, _ in covered))
+        hit = self._plans.get(kind)
+        if hit is None or hit[0] != sig:
+            hit = self._plans[kind] = (sig, build())
+        return hit[1]
+
+    def mark_current(self, covered) -> None:
+        """A fused optimiser step wrote the parameters AND the covered weights' next parts and maxima: everything else
+        derived from the parameters is stale, these already describe the new values."""
+        params_changed()
+        for _, ent, w in covered:
+            ent.stamp(w)
+
+
+_STORES = {}  # Tensor.get_device() -> _WeightStore (the device's index: every conv asks, and hashing a torch.device costs more)
+
+
+def _device_index(device) -> int:
+    """What Tensor.get_device() gives for a tensor on `device` ("cuda" without an index: the current device)."""
+    device = torch.device(device)
+    if device.type == "cpu":
+        return -1
+    return torch.cuda.current_device() if device.index is None else device.index
+
+
+def _store(device) -> _WeightStore:
+    key = _device_index(device)
+    store = _STORES.get(key)
+    if store is None:
+        store = _STORES[key] = _WeightStore(device)
+    return store
+
+
+def weight_entry(weight: torch.Tensor) -> Optional[_WeightParts]:
+    """The weight's registry entry (`parts`, `slot`, `exact`, `exact_ok`, `current(weight)`: to look at, not to change), or
+    None when it was never registered."""
+    store = _STORES.get(weight.get_device())
+    ent = None if store is None else store.entries.get(id(weight))
+    return ent if ent is not None and ent.ref() is weight else None
+
+
+def registered_weights(device):
+    """[(entry, weight)] of the device's live registered weights (see weight_entry)."""
+    store = _STORES.get(_device_index(device))
+    return [] if store is None else list(store.live())
+
+
+def free_weight_slots(device) -> int:
+    """How many more weights the device's store can register."""
+    store = _STORES.get(_device_index(device))
+    return _STORE_SLOTS if store is None else len(store.free)
+
+
+def _flat_layout(total: int, spans):
+    """The ranges of a flat buffer of `total` floats around the weights `spans` = [(first element, numel)] given in flat
+    order: [(begin4, n4, i)] in units of FOUR floats, in order, tiling [0, total) exactly once -- i: the range is weight
+    i's span, None: a gap between weights (biases, BatchNorm affines, unregistered weights, the padding at the end); no
+    empty ranges.  None for a layout the range tables do not describe: a buffer that is not whole 16-byte rows, a span
+    that is not, spans that overlap (the merged mu | logvar head registered next to its own two halves) or reach past the
+    end.  (The two walks this replaces differed only where no input can: a registered view always lies inside the buffer,
+    and rounding the tail up to four floats did nothing once `total % 4 == 0`.)"""
+    if total % 4:
+        return None
+    ranges, pos = [], 0
+    for i, (off, n) in enumerate(spans):
+        if off % 4 or n % 4 or off < pos or off + n > total:
+            return None
+        if off > pos:
+            ranges.append((pos // 4, (off - pos) // 4, None))
+        ranges.append((off // 4, n // 4, i))
+        pos = off + n
+    if pos < total:
+        ranges.append((pos // 4, (total - pos) // 4, None))
+    return ranges
 
 
 # Fused optimiser step: for the conv weights that live in the model's flat parameter buffer and run on the split-precision
@@ -641,28 +812,60 @@ def adam_step_bound(beta1: float, beta2: float):
     return _ADAM_BOUNDS[key]
 
 
-def _wp_covered(flat):
-    """[(first flat element, entry, weight)] of the registered split-precision weights that live in the flat parameter buffer
-    (16-byte aligned, [Cout][k][k][Cin] memory; not the zero-padded copies), in flat order -- None as soon as one of them
-    has parts or a maximum that are not current (first steps, new registrations): a fused optimiser step must wait."""
+# late: (first job, jobs, workgroup blocks, [(offset, numel)]) per late set -- the early jobs come first in the table, then
+# set by set, and every launch numbers its own blocks from 0
+_AdamPlan = collections.namedtuple("_AdamPlan", "jobs n_jobs n_early blocks late ranges n_ranges rblocks idx")
+
+
+def _plan_adam(flat, grad, m, v, covered, late_from, late_sets):
+    """fused_adam_step's tables for these buffers: one AdamFragJob per covered weight, one AdamRange per gap between them,
+    the weights' cells for rac_amax_bound.  None for a layout they do not describe."""
+    layout = _flat_layout(flat.numel(), [(off, w.numel()) for off, _, w in covered])
+    if layout is None:
+        return None
+    lib = _lib.load()
     dev = flat.device
-    base, nbytes = flat.data_ptr(), flat.numel() * 4
-    covered = []
-    for ent in _WP_ENTRIES.values():
-        if ent.device != dev:
-            continue
-        w = ent.ref()
-        if w is None or getattr(w, "_rac_pad_source", None) is not None:
-            continue
-        off = w.data_ptr() - base
+
+    def late_group(off, w):  # index of the weight's late set, -1: updated on the caller's stream
+        if late_from is None or off < late_from:
+            return -1
+        for gi, ptrs in enumerate(late_sets):
+            if w.data_ptr() in ptrs:
+                return gi
+        return -1
+    groups = [late_group(off, w) for off, _, w in covered]
+    n_early = groups.count(-1)
+    n_in = [groups.count(gi) for gi in range(len(late_sets))]
+    first = [n_early + sum(n_in[:gi]) for gi in range(len(late_sets))]
+    taken, late_blocks, late_spans = [0] * len(late_sets), [0] * len(late_sets), [[] for _ in late_sets]
+    jobs = (AdamFragJob * len(covered))()
+    ne = blocks = 0
+    for (off, ent, w), gi in zip(covered, groups):
         co, ci, k, _ = w.shape
-        if not (0 <= off < nbytes and off % 16 == 0 and w.stride() == (k * k * ci, 1, k * ci, ci)):
-            continue
-        if ent.tag != _wp_tag(w) or not ent.exact_ok:
-            return None
-        covered.append((off // 4, ent, w))
-    covered.sort(key=lambda c: c[0])
-    return covered
+        n, nb = w.numel(), lib.rac_weight_frag_blocks(co, ci, k)
+        if gi >= 0:
+            at, begin = first[gi] + taken[gi], late_blocks[gi]
+            taken[gi] += 1
+            late_blocks[gi] += nb
+            late_spans[gi].append((off, n))
+        else:
+            at, begin = ne, blocks
+            ne += 1
+            blocks += nb
+        jobs[at] = AdamFragJob(p=flat.data_ptr() + 4 * off, g=grad.data_ptr() + 4 * off, m=m.data_ptr() + 4 * off,
+                               v=v.data_ptr() + 4 * off, scale_slot=ptr(ent.slot), amax_out=ptr(ent.exact),
+                               parts_fwd=ptr(ent.parts.get(False)), parts_t=ptr(ent.parts.get(True)), part_stride=n,
+                               Cout=co, Cin=ci, ksize=k, reserved=0, block_begin=begin)
+    gaps = [(b4, n4) for b4, n4, i in layout if i is None]
+    rjobs = (AdamRange * max(1, len(gaps)))()
+    rblocks = 0
+    for j, (b4, n4) in enumerate(gaps):
+        rjobs[j] = AdamRange(begin4=b4, n4=n4, block_begin=rblocks)
+        rblocks += _cdiv(n4, 1024)
+    return _AdamPlan(jobs=_upload_jobs(jobs, dev), n_jobs=len(covered), n_early=n_early, blocks=blocks,
+                     late=list(zip(first, n_in, late_blocks, late_spans)), ranges=_upload_jobs(rjobs, dev),
+                     n_ranges=len(gaps), rblocks=rblocks,
+                     idx=torch.tensor([ent.idx for _, ent, _ in covered], device=dev, dtype=torch.int32))
 
 
 def fused_adam_step(flat, grad, m, v, lr, beta1, beta2, eps, step, late=None):
@@ -677,121 +880,53 @@ def fused_adam_step(flat, grad, m, v, lr, beta1, beta2, eps, step, late=None):
     [(event, [(offset, numel)]) per set] -- the event the consumer of those weights must wait for -- instead of True: the pass is
     bound by HBM (8.6 GB per step), the next step's encoder forward is many small launches bound by latency; the caller
     (optim.FusedAdam with `overlap_next_forward`) makes the model wait behind its encoder."""
-    global PARAM_EPOCH
     if not ADAM_FUSED:
         return False
     bound = adam_step_bound(beta1, beta2)
     if bound is None:
         return False
-    dev = flat.device
-    st = _wp_state(dev)
-    base = flat.data_ptr()
-    covered = _wp_covered(flat)
+    store = _store(flat.device)
+    covered = store.covered(flat)
     if not covered:
         return False
     # late[1]: one set of data pointers, or a LIST of sets = groups in the order the next forward pass needs them (each
     # group its own launch and event on the side stream, which runs them in that order)
+    late_from = None if late is None else late[0]
     late_sets = [] if late is None else (list(late[1]) if isinstance(late[1], (list, tuple)) else [late[1]])
-
-    def late_group(off, w):  # index of the weight's late group, -1: updated on the caller's stream
-        if late is None or off < late[0]:
-            return -1
-        for gi, ptrs in enumerate(late_sets):
-            if w.data_ptr() in ptrs:
-                return gi
-        return -1
-    is_late = lambda off, w: late_group(off, w) >= 0
-    sig = (base, grad.data_ptr(), m.data_ptr(), v.data_ptr(),
-           None if late is None else (late[0], tuple(tuple(sorted(ps)) for ps in late_sets)),
-           tuple((off, ent.idx, tuple(sorted((t, q.data_ptr()) for t, q in ent.parts.items()))) for off, ent, _ in covered))
-    plan = st["adam_plan"]
-    if plan is not None and plan["sig"] == sig and plan.get("unsupported"):
+    plan = store.plan("adam", (flat.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), late_from,
+                               tuple(tuple(sorted(ps)) for ps in late_sets)), covered,
+                      lambda: _plan_adam(flat, grad, m, v, covered, late_from, late_sets))
+    if plan is None:  # not the fused pass's layout: plain Adam, parts refreshed lazily
         return False
-    if plan is None or plan["sig"] != sig:
-        lib = _lib.load()
-        jobs = (AdamFragJob * len(covered))()
-        groups = [late_group(off, w) for off, _, w in covered]
-        n_early = sum(1 for gi in groups if gi < 0)
-        n_in = [sum(1 for gi in groups if gi == k) for k in range(len(late_sets))]
-        first = [n_early + sum(n_in[:k]) for k in range(len(late_sets))]  # a group's first slot in the job table
-        slot_of, taken = {}, [0] * len(late_sets)  # the early jobs first, then group by group (each numbers its own blocks)
-        ne = 0
-        for j, gi in enumerate(groups):
-            if gi >= 0:
-                slot_of[j], taken[gi] = first[gi] + taken[gi], taken[gi] + 1
-            else:
-                slot_of[j], ne = ne, ne + 1
-        ranges, blocks, pos = [], 0, 0
-        late_blocks = [0] * len(late_sets)
-        late_spans = [[] for _ in late_sets]
-        for i, (off, ent, w) in enumerate(covered):
-            co, ci, k, _ = w.shape
-            n = w.numel()
-            if off % 4 or n % 4 or off < pos or flat.numel() % 4:
-                # registered views that overlap (the merged mu | logvar head next to its own two parameters) or are not
-                # 16-byte aligned: this layout is not the fused pass's -- plain Adam, parts refreshed lazily
-                st["adam_plan"] = {"sig": sig, "unsupported": True}
-                return False
-            if off > pos:
-                ranges.append((pos // 4, (off - pos) // 4))
-            pos = off + n
-            gi = groups[i]
-            lt = gi >= 0
-            jobs[slot_of[i]] = AdamFragJob(p=base + 4 * off, g=grad.data_ptr() + 4 * off, m=m.data_ptr() + 4 * off,
-                                           v=v.data_ptr() + 4 * off, scale_slot=ptr(ent.slot),
-                                           amax_out=ptr(st["exact"][ent.idx:ent.idx + 1]), parts_fwd=ptr(ent.parts.get(False)),
-                                           parts_t=ptr(ent.parts.get(True)), part_stride=n, Cout=co, Cin=ci, ksize=k, reserved=0,
-                                           block_begin=late_blocks[gi] if lt else blocks)
-            if lt:
-                late_blocks[gi] += lib.rac_weight_frag_blocks(co, ci, k)
-                late_spans[gi].append((off, n))
-            else:
-                blocks += lib.rac_weight_frag_blocks(co, ci, k)
-        if pos < flat.numel():
-            ranges.append((pos // 4, (flat.numel() - pos + 3) // 4))
-        rjobs = (AdamRange * max(1, len(ranges)))()
-        rblocks = 0
-        for i, (b4, n4) in enumerate(ranges):
-            rjobs[i] = AdamRange(begin4=b4, n4=n4, block_begin=rblocks)
-            rblocks += _cdiv(n4, 1024)
-        plan = st["adam_plan"] = {
-            "sig": sig, "jobs": _wp_upload(jobs, dev), "n_jobs": len(covered), "blocks": blocks,
-            "n_early": n_early, "late_blocks": late_blocks, "late_spans": late_spans, "late_first": first, "late_n": n_in,
-            "ranges": _wp_upload(rjobs, dev), "n_ranges": len(ranges), "rblocks": rblocks,
-            "idx": torch.tensor([ent.idx for _, ent, _ in covered], device=dev, dtype=torch.int32)}
     sp = stream_ptr()
-    call("rac_amax_bound", ptr(st["exact"]), ptr(st["slots"]), ptr(plan["idx"]), plan["n_jobs"],
-         float(lr) * bound * 1.01, sp)
-    n_early, n_late = plan["n_early"], plan["n_jobs"] - plan["n_early"]
+    call("rac_amax_bound", ptr(store.exact), ptr(store.slots), ptr(plan.idx), plan.n_jobs, float(lr) * bound * 1.01, sp)
+    n_early, n_late = plan.n_early, plan.n_jobs - plan.n_early
     if n_early and ADAM_WGS:
-        call("rac_adam_frag_multi_bounded", ptr(plan["jobs"]), n_early, plan["blocks"], ADAM_WGS, float(lr), float(beta1),
+        call("rac_adam_frag_multi_bounded", ptr(plan.jobs), n_early, plan.blocks, ADAM_WGS, float(lr), float(beta1),
              float(beta2), float(eps), int(step), sp)
     elif n_early:
-        call("rac_adam_frag_multi", ptr(plan["jobs"]), n_early, plan["blocks"], float(lr), float(beta1), float(beta2),
+        call("rac_adam_frag_multi", ptr(plan.jobs), n_early, plan.blocks, float(lr), float(beta1), float(beta2),
              float(eps), int(step), sp)
-    if plan["n_ranges"]:
-        call("rac_adam_ranges", ptr(flat), ptr(grad), ptr(m), ptr(v), ptr(plan["ranges"]), plan["n_ranges"],
-             plan["rblocks"], float(lr), float(beta1), float(beta2), float(eps), int(step), sp)
+    if plan.n_ranges:
+        call("rac_adam_ranges", ptr(flat), ptr(grad), ptr(m), ptr(v), ptr(plan.ranges), plan.n_ranges,
+             plan.rblocks, float(lr), float(beta1), float(beta2), float(eps), int(step), sp)
     done = []
     if n_late:
         main = torch.cuda.current_stream()
-        side = _side_stream("adam", dev)  # the late weights' update runs here
+        side = _side_stream("adam", flat.device)  # the late weights' update runs here
         ready = torch.cuda.Event()
         ready.record(main)  # every gradient, the scale bounds and whatever read the old weights precede the side launch
         side.wait_event(ready)
         with torch.cuda.stream(side):
-            for gi, n_g in enumerate(plan["late_n"]):
+            for first, n_g, blocks_g, spans in plan.late:
                 if not n_g:
                     continue
-                call("rac_adam_frag_multi_bounded", ptr(plan["jobs"]) + plan["late_first"][gi] * C.sizeof(AdamFragJob), n_g,
-                     plan["late_blocks"][gi], ADAM_LATE_WGS, float(lr), float(beta1), float(beta2), float(eps), int(step),
-                     stream_ptr())
+                call("rac_adam_frag_multi_bounded", ptr(plan.jobs) + first * C.sizeof(AdamFragJob), n_g, blocks_g,
+                     ADAM_LATE_WGS, float(lr), float(beta1), float(beta2), float(eps), int(step), stream_ptr())
                 ev = torch.cuda.Event()
                 ev.record(side)
-                done.append((ev, list(plan["late_spans"][gi])))
-    PARAM_EPOCH += 1
-    for _, ent, w in covered:  # their parts and maxima already describe the new values
-        ent.tag = _wp_tag(w)
+                done.append((ev, list(spans)))
+    store.mark_current(covered)
     return done if done else True
 
 
@@ -801,91 +936,63 @@ def fused_adam_step(flat, grad, m, v, lr, beta1, beta2, eps, step, late=None):
 # for the maxima (rac_absmax_multi) is gone, the fragment pass stays.  No single pass in the manner of fused_adam_step:
 # it needs a bound of the step BEFORE the new maximum is known, RMSprop's only rigorous one is lr / sqrt(1 - alpha) (0.1 at
 # torch's defaults: the size of the weights) and SGD has none -- a scale from such a bound would drop operand bits.
+_OptimPlan = collections.namedtuple("_OptimPlan", "ranges n_ranges rblocks frag n_frag frag_blocks idx")
+
+
+def _plan_optim(store, flat, covered):
+    """fused_optim_step's tables: one OptimRange per range of the layout (a covered weight's carries its amax slot) and
+    the fragment jobs of the covered weights.  None for a layout they do not describe."""
+    layout = _flat_layout(flat.numel(), [(off, w.numel()) for off, _, w in covered])
+    if layout is None:
+        return None
+    rjobs = (OptimRange * len(layout))()
+    rblocks = 0
+    for j, (b4, n4, i) in enumerate(layout):
+        rjobs[j] = OptimRange(begin4=b4, n4=n4, block_begin=rblocks, amax=None if i is None else ptr(covered[i][1].slot))
+        rblocks += _cdiv(n4, 1024)
+    _, _, _, tf, nf, fb, idx = store.tables([(ent, w) for _, ent, w in covered])
+    return _OptimPlan(ranges=_upload_jobs(rjobs, flat.device), n_ranges=len(layout), rblocks=rblocks, frag=tf, n_frag=nf,
+                      frag_blocks=fb, idx=idx)
+
+
 def fused_optim_step(rule, flat, grad, state0, state1, lr, momentum=0.0, gain=1.0, alpha=0.0, eps=0.0, flags=0):
     """One RMSprop / SGD step (include/rac_hip.h: rac_optim_step's rules and arguments; state tensors a rule does not have
     are None) over the flat buffers that leaves the registered split-precision weights' maxima and parts current.  False
     (nothing launched) when that is not possible yet -- a weight whose parts or maximum are not current (first steps, new
     registrations), no registered weight inside `flat`, a layout the table does not describe: the caller then takes
-    rac_optim_step over the flat buffer and the parts are refreshed lazily (_wp_refresh)."""
-    global PARAM_EPOCH
-    dev = flat.device
-    st = _wp_state(dev)
-    base = flat.data_ptr()
-    covered = _wp_covered(flat)
+    rac_optim_step over the flat buffer and the parts are refreshed lazily (_WeightStore.refresh)."""
+    store = _store(flat.device)
+    covered = store.covered(flat)
     if not covered:
         return False
-    sig = (base, grad.data_ptr(), ptr(state0), ptr(state1),
-           tuple((off, ent.idx, tuple(sorted((t, q.data_ptr()) for t, q in ent.parts.items()))) for off, ent, _ in covered))
-    plan = st["optim_plan"]
-    if plan is not None and plan["sig"] == sig and plan.get("unsupported"):
+    plan = store.plan("optim", (flat.data_ptr(), grad.data_ptr(), ptr(state0), ptr(state1)), covered,
+                      lambda: _plan_optim(store, flat, covered))
+    if plan is None:  # not this table's layout: the plain step, parts refreshed lazily (as fused_adam_step)
         return False
-    if plan is None or plan["sig"] != sig:
-        ranges, pos = [], 0
-        for off, ent, w in covered:
-            n = w.numel()
-            if off % 4 or n % 4 or off < pos or off + n > flat.numel() or flat.numel() % 4:
-                # registered views that overlap (the merged mu | logvar head next to its own two parameters) or are not
-                # 16-byte aligned: not this table's layout -- the plain step, parts refreshed lazily (as fused_adam_step)
-                st["optim_plan"] = {"sig": sig, "unsupported": True}
-                return False
-            if off > pos:
-                ranges.append((pos // 4, (off - pos) // 4, None))
-            ranges.append((off // 4, n // 4, ptr(ent.slot)))
-            pos = off + n
-        if pos < flat.numel():
-            ranges.append((pos // 4, (flat.numel() - pos) // 4, None))
-        rjobs = (OptimRange * len(ranges))()
-        rblocks = 0
-        for i, (b4, n4, slot) in enumerate(ranges):
-            rjobs[i] = OptimRange(begin4=b4, n4=n4, block_begin=rblocks, amax=slot)
-            rblocks += _cdiv(n4, 1024)
-        _, _, _, tf, nf, fb, idx = _wp_tables(st, [(ent, w) for _, ent, w in covered], dev)
-        plan = st["optim_plan"] = {"sig": sig, "ranges": _wp_upload(rjobs, dev), "n_ranges": len(ranges), "rblocks": rblocks,
-                                   "frag": tf, "n_frag": nf, "frag_blocks": fb, "idx": idx}
     sp = stream_ptr()
-    idx = plan["idx"]
-    st["slots"].index_fill_(0, idx, 0)  # the update folds the new maxima into zeroed slots
-    call("rac_optim_ranges", ptr(flat), ptr(grad), ptr(state0), ptr(state1), ptr(plan["ranges"]), plan["n_ranges"],
-         plan["rblocks"], int(rule), int(flags), float(lr), float(momentum), float(gain), float(alpha), float(eps), sp)
-    call("rac_weight_frag_split_multi", ptr(plan["frag"]), plan["n_frag"], plan["frag_blocks"], sp)
-    st["exact"].index_copy_(0, idx, st["slots"].index_select(0, idx))
-    PARAM_EPOCH += 1
-    for _, ent, w in covered:  # their parts and maxima already describe the new values
-        ent.tag = _wp_tag(w)
+    idx = plan.idx
+    store.slots.index_fill_(0, idx, 0)  # the update folds the new maxima into zeroed slots
+    call("rac_optim_ranges", ptr(flat), ptr(grad), ptr(state0), ptr(state1), ptr(plan.ranges), plan.n_ranges,
+         plan.rblocks, int(rule), int(flags), float(lr), float(momentum), float(gain), float(alpha), float(eps), sp)
+    call("rac_weight_frag_split_multi", ptr(plan.frag), plan.n_frag, plan.frag_blocks, sp)
+    store.exact.index_copy_(0, idx, store.slots.index_select(0, idx))
+    store.mark_current(covered)
     return True
 
 
 def weight_parts(weight: torch.Tensor, transposed: bool = False):
     """(fp16 parts of weight * 2^k in MFMA fragment order, amax slot), kept until the parameter changes;
     `transposed`: of the (Cin, Cout) tap-flipped weight whose forward conv is the data gradient."""
-    key = id(weight)
-    ent = _WP_ENTRIES.get(key)
-    if ent is None or ent.ref() is not weight or ent.device != weight.device:
-        st = _wp_state(weight.device)
-        if not st["free"]:
-            raise _lib.RacError("too many conv weights registered for the split-precision pipe")
-        co, ci, k, _ = weight.shape
-        if co % 32 or ci % 32:
-            raise _lib.RacError(f"split-precision weight {tuple(weight.shape)}: channel counts must be multiples of 32")
-        ent = _WeightParts()
-        ent.idx = st["free"].pop()
-        ent.device, ent.parts, ent.tag, ent.exact_ok = weight.device, {}, None, False
-        ent.slot = st["slots"][ent.idx:ent.idx + 1]
-        ent.ref = weakref.ref(weight, functools.partial(_wp_drop, key, weight.device, ent.idx))
-        _WP_ENTRIES[key] = ent
+    store = _STORES.get(weight.get_device()) or _store(weight.device)
+    ent = store.entries.get(id(weight))
+    if ent is None or ent.ref() is not weight:
+        ent = store.register(weight)
     if transposed not in ent.parts:
-        parts = torch.empty((2, weight.numel()), device=weight.device, dtype=torch.float16)
-        parts._rac_transposed = transposed
-        ent.parts[transposed] = parts
-        ent.tag = None
-    if ent.tag != _wp_tag(weight):
-        gate = PARAM_GATE
-        if gate is not None:  # this weight's new values may still be travelling (a sharded optimiser's all-gather)
-            src = getattr(weight, "_rac_pad_source", None)
-            base = src[0]() if src is not None else weight
-            if base is not None and not gate.ready(base):
-                gate.wait_params()
-        _wp_refresh(weight.device)
+        ent.add_parts(weight, transposed)
+    if not ent.current(weight):
+        if ent.in_flight():  # this weight's new values may still be travelling (a sharded optimiser's all-gather)
+            PARAM_GATE.wait_params()
+        store.refresh()
     return ent.parts[transposed], ent.slot
 
 

@@ -30,6 +30,16 @@ def _require_storage_shapes(opt, names):
                                  % (name, tuple(t.shape), tuple(p.shape)))
 
 
+def _flat_span(model, t: torch.Tensor):
+    """(first, end) flat elements of the parameter memory `t` in the model's flat parameter buffer; None when `t` is not a
+    view of it."""
+    flat, _ = model.flat_parameters()
+    lo = (t.data_ptr() - flat.data_ptr()) // 4
+    if lo < 0 or lo >= flat.numel():
+        return None
+    return lo, lo + t.numel()
+
+
 class FusedAdam(torch.optim.Optimizer):
     # The pass is bound by HBM (8.6 GB per step at g512: ~1.7 ms); the forward pass that follows starts with the encoder's
     # many small launches (2.2 ms, bound by latency, reading only the encoder's parameters).  With `overlap_next_forward` the
@@ -57,34 +67,27 @@ class FusedAdam(torch.optim.Optimizer):
             return
         torch.cuda.current_stream().wait_event(self._late[-1][0])  # (one in-order side stream: the last event covers all)
         self._late = []
-        if ops.PARAM_GATE is self:
-            ops.PARAM_GATE = None
+        ops.release_gate(self)
 
     def wait_for(self, t: torch.Tensor):
         """... for the late group that holds the parameter memory `t` (and the groups in front of it: one stream)."""
-        if not self._late:
+        span = _flat_span(self._model, t) if self._late else None
+        if span is None:
             return
-        flat, _ = self._model.flat_parameters()
-        lo = (t.data_ptr() - flat.data_ptr()) // 4
-        if lo < 0 or lo >= flat.numel():
-            return  # not a view of this model's flat parameter buffer
-        hi = lo + t.numel()
+        lo, hi = span
         hit = [k for k, (_, spans) in enumerate(self._late) if any(off < hi and lo < off + n for off, n in spans)]
         if not hit:
             return
         torch.cuda.current_stream().wait_event(self._late[hit[-1]][0])
         self._late = self._late[hit[-1] + 1:]
-        if not self._late and ops.PARAM_GATE is self:
-            ops.PARAM_GATE = None
+        if not self._late:
+            ops.release_gate(self)
 
     def ready(self, t: torch.Tensor) -> bool:
-        if not self._late:
+        span = _flat_span(self._model, t) if self._late else None
+        if span is None:
             return True
-        flat, _ = self._model.flat_parameters()
-        lo = (t.data_ptr() - flat.data_ptr()) // 4
-        if lo < 0 or lo >= flat.numel():
-            return True  # not a view of this model's flat parameter buffer
-        hi = lo + t.numel()
+        lo, hi = span
         return all(not (off < hi and lo < off + n) for _, spans in self._late for off, n in spans)
 
     def _late_group(self):
@@ -138,7 +141,7 @@ class FusedAdam(torch.optim.Optimizer):
                 self._late = list(res)
                 ops.PARAM_GATE = self
             return
-        ops.PARAM_EPOCH += 1  # invalidates caches derived from the parameters (padded weight copies, operand parts)
+        ops.params_changed()  # invalidates caches derived from the parameters (padded weight copies, operand parts)
         _lib.call("rac_adam_step", flat.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), flat.numel(),
                   float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), self._steps,
                   _lib.stream_ptr())
@@ -196,7 +199,7 @@ class ShardedAdam(FusedAdam):
                  encoder's forward pass (`SVGConvModel._encode`: `wait_params(upto=...)`, then `wait_params()`), so the
                  ConvLSTM weights' 90 % of the bytes travel under the encoder; state_dict waits for everything.
 
-    The conv weights' split-precision operand parts are refreshed lazily after the all-gather (ops._wp_refresh: one
+    The conv weights' split-precision operand parts are refreshed lazily after the all-gather (ops._WeightStore.refresh: one
     absmax + one fragment-split launch over all weights) -- the fused Adam + parts pass needs the whole updated weight.
     Same arithmetic per element as FusedAdam (`rac_adam_step` on slices), so a one-rank group reproduces it bit for bit."""
 
@@ -235,24 +238,20 @@ class ShardedAdam(FusedAdam):
             else:
                 keep.append((start, size, work))
         self._pending = keep
-        if not keep and ops.PARAM_GATE is self:
-            ops.PARAM_GATE = None
+        if not keep:
+            ops.release_gate(self)
 
     def wait_for(self, t: torch.Tensor):
         """(the all-gather's buckets complete in issue order: waiting for a parameter is waiting for the buckets up to its end)"""
         if not self.ready(t):
-            flat, _ = self._model.flat_parameters()
-            self.wait_params(upto=(t.data_ptr() - flat.data_ptr()) // 4 + t.numel())
+            self.wait_params(upto=_flat_span(self._model, t)[1])
 
     def ready(self, t: torch.Tensor) -> bool:
         """Have the buckets overlapping the parameter memory `t` been waited for?"""
-        if not self._pending:
+        span = _flat_span(self._model, t) if self._pending else None
+        if span is None:
             return True
-        flat, _ = self._model.flat_parameters()
-        lo = (t.data_ptr() - flat.data_ptr()) // 4
-        if lo < 0 or lo >= flat.numel():
-            return True  # not a view of the flat parameter buffer
-        hi = lo + t.numel()
+        lo, hi = span
         return all(not (start < hi and lo < start + size) for start, size, _ in self._pending)
 
     @torch.no_grad()
@@ -292,8 +291,8 @@ class ShardedAdam(FusedAdam):
             work = dist.all_gather_into_tensor(flat[start:start + size], flat[start + rank * n:start + (rank + 1) * n],
                                                async_op=True)
             self._pending.append((start, size, work))
-        ops.PARAM_EPOCH += 1  # caches derived from the parameters (padded copies, operand parts) are stale
-        ops.PARAM_GATE = self  # ... and are refreshed bucket by bucket as the all-gather is waited for (ops._wp_refresh)
+        ops.params_changed()  # caches derived from the parameters (padded copies, operand parts) are stale
+        ops.PARAM_GATE = self  # ... and are refreshed bucket by bucket as the all-gather is waited for (_WeightStore.refresh)
 
     # torch.optim.Adam-compatible state: the full moments are assembled from all ranks' slices
     def _moments(self):
@@ -401,7 +400,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
             ops.finish_grads()
         if ops.fused_optim_step(self._RULE, flat, grad, s0, s1, g["lr"], momentum, gain, alpha, eps, flags):
             return
-        ops.PARAM_EPOCH += 1  # invalidates caches derived from the parameters (padded weight copies, operand parts)
+        ops.params_changed()  # invalidates caches derived from the parameters (padded weight copies, operand parts)
         _lib.call("rac_optim_step", flat.data_ptr(), grad.data_ptr(), _lib.ptr(s0), _lib.ptr(s1), flat.numel(), self._RULE,
                   int(flags), float(g["lr"]), float(momentum), float(gain), float(alpha), float(eps), _lib.stream_ptr())
 

@@ -936,8 +936,7 @@ class PredictionTrainer(object):
         # nothing of this loop's optimiser stays installed behind it (ops.PARAM_GATE is process-global: it would pin the
         # trainer's 4 GB and be asked about the next model's parameters)
         self.optimizer.wait_params()
-        if ops.PARAM_GATE is self.optimizer:
-            ops.PARAM_GATE = None
+        ops.release_gate(self.optimizer)
         return info
 
     def train_copy_baseline(self, train_loader=None, test_loader=None, transfer_loader=None):

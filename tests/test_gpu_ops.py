@@ -972,12 +972,10 @@ def test_fused_adam_step_writes_the_next_parts(dev):
                   0.999, 1e-8, step, _lib.stream_ptr())
         assert ops.fused_adam_step(flat, grad, m, v, lr, 0.9, 0.999, 1e-8, step)
         assert torch.equal(flat, ref[0]) and torch.equal(m, ref[1]) and torch.equal(v, ref[2])
-        st = ops._wp_state(dev)
         for w, both in zip(ws, (True, True, False)):
-            ent = ops._WP_ENTRIES[id(w)]
-            assert ent.tag == ops._wp_tag(w)  # no lazy refresh will follow
-            exact = st["exact"][ent.idx:ent.idx + 1]
-            assert int(exact.item()) == int(w.abs().max().view(torch.int32).item())
+            ent = ops.weight_entry(w)
+            assert ent.current(w)  # no lazy refresh will follow
+            assert int(ent.exact.item()) == int(w.abs().max().view(torch.int32).item())
             bound = ent.slot.view(torch.float32)
             assert float(w.abs().max()) <= float(bound) <= float(w.abs().max()) + 10 * lr
             co, ci, k, _ = w.shape
@@ -996,8 +994,8 @@ def test_fused_adam_step_writes_the_next_parts(dev):
     # event the buffers and the parts are the bits of the one-stream pass
     keep = [t.clone() for t in (flat, m, v)]
     assert ops.fused_adam_step(flat, grad, m, v, 1e-3, 0.9, 0.999, 1e-8, 4) is True
-    want = [t.clone() for t in (flat, m, v)] + [q.clone() for w in ws for q in ops._WP_ENTRIES[id(w)].parts.values()]
-    want_slots = [ops._WP_ENTRIES[id(w)].slot.clone() for w in ws]
+    want = [t.clone() for t in (flat, m, v)] + [q.clone() for w in ws for q in ops.weight_entry(w).parts.values()]
+    want_slots = [ops.weight_entry(w).slot.clone() for w in ws]
     for t, k0 in zip((flat, m, v), keep):
         t.copy_(k0)
     for w in ws:  # (the restored weights' parts: the lazy path, as after load_state_dict)
@@ -1009,9 +1007,9 @@ def test_fused_adam_step_writes_the_next_parts(dev):
     span = lambda w: ((w.data_ptr() - flat.data_ptr()) // 4, w.numel())
     assert res is not True and [sp for _, sp in res] == [[span(ws[2])], [span(ws[1])]]
     torch.cuda.current_stream().wait_event(res[-1][0])  # (one in-order stream: the last event covers every group)
-    got = [flat, m, v] + [q for w in ws for q in ops._WP_ENTRIES[id(w)].parts.values()]
+    got = [flat, m, v] + [q for w in ws for q in ops.weight_entry(w).parts.values()]
     assert all(torch.equal(a, b) for a, b in zip(got, want))
-    assert all(torch.equal(ops._WP_ENTRIES[id(w)].slot, sl) for w, sl in zip(ws, want_slots))
+    assert all(torch.equal(ops.weight_entry(w).slot, sl) for w, sl in zip(ws, want_slots))
     # a weight changed behind the parts' back (load_state_dict ...): the fused step declines, the lazy refresh repairs
     ws[0].mul_(2.0)
     assert not ops.fused_adam_step(flat, grad, m, v, 1e-3, 0.9, 0.999, 1e-8, 5)

@@ -195,9 +195,8 @@ def registered_in(flat):
     """[(entry, weight)] of the split-precision weights that live in the flat parameter buffer."""
     from robot_aware_control_amd import ops
     out = []
-    for ent in ops._WP_ENTRIES.values():
-        w = ent.ref()
-        if w is None or w.device != flat.device or getattr(w, "_rac_pad_source", None) is not None:
+    for ent, w in ops.registered_weights(flat.device):
+        if getattr(w, "_rac_pad_source", None) is not None:
             continue
         if 0 <= w.data_ptr() - flat.data_ptr() < flat.numel() * 4:
             out.append((ent, w))
@@ -224,7 +223,7 @@ def test_no_stale_operands_after_a_table_step(dev, weights, optimizer, monkeypat
     entries = registered_in(flat)
     assert len(entries) >= 10
     for ent, w in entries:
-        assert ent.tag == ops._wp_tag(w) and ent.exact_ok
+        assert ent.current(w) and ent.exact_ok
         assert int(ent.slot) == int(w.detach().abs().max().view(torch.int32)), tuple(w.shape)
         co, ci, k, _ = w.shape
         for transposed, parts in ent.parts.items():

@@ -33,7 +33,7 @@ def run(overlap):
         torch.cuda.synchronize()
         flat, grad = tr.model.flat_parameters()
         snaps.append((flat.detach().cpu().clone(), grad.detach().cpu().clone(), dict(losses), late))
-    ops.PARAM_GATE = None
+    ops.release_gate(tr.optimizer)
     return snaps, tr
 
 
